@@ -1,7 +1,8 @@
 """Benchmark harness (driver contract — see project brief).
 
-Measures BOTH halves of the BASELINE.json metric ("inference bases/sec +
-train windows/sec at b=128") on N GPUs of one node, by default as two timed
+Measures the BASELINE.json metric ("inference bases/sec + train windows/sec
+at b=128") on N GPUs of one node. A plain run times the headline inference
+section only; --full adds the train section in front of it, as two timed
 sections of one invocation:
 
   * train: the fused HIP train step (the same path the roko_amd.train CLI
@@ -10,10 +11,15 @@ sections of one invocation:
     path, fused argmax, predictions copied to host (bases = windows *
     30-column stride).
 
-  python bench.py --gpus N --steps K --warmup W [--mode both|inference|train]
+  python bench.py --gpus N --steps K --warmup W [--full]
+                  [--mode both|inference|train] [--dump-outputs DIR]
 
 One JSON line is printed per section; the LAST line is the inference record
-(comparable round to round) and it carries the train numbers in its config.
+(comparable round to round) and under --full it carries the train numbers in
+its config. --dump-outputs DIR writes what the timed path returned in its
+last timed step as DIR/<name>.npy (float32), plus the logits of that step's
+final batch; inputs and weights are seeded, so two builds can be compared
+output for output.
 Under torchrun (one rank per GPU, RCCL) inference ranks run independent
 batch streams (weak scaling; no collectives — SURVEY.md §2.5); train ranks
 all-reduce gradients each step (weak scaling: global batch = 128 * N). Max
@@ -39,6 +45,18 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from roko_amd import config as C
 from roko_amd.model import RokoModel
 from roko_amd.parallel.ddp import init_distributed
+
+
+def _dump(args, rank, name, t):
+    """Write one output of the timed path as <dir>/<name>.npy in float32
+    (rank 0 keeps the bare name; other ranks append their rank)."""
+    import numpy as np
+
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    if rank:
+        name = f"{name}_rank{rank}"
+    np.save(os.path.join(args.dump_outputs, name + ".npy"),
+            t.detach().to("cpu", torch.float32).numpy())
 
 
 def bench_inference(args, rank, world, device):
@@ -70,13 +88,17 @@ def bench_inference(args, rank, world, device):
     # ~3% of the measurement; the 120 s soak is the steady-state truth.)
     BATCHES_PER_STEP = 32 if pipe is not None else 1
     if pipe is not None:
-        def step(i):
+        def step(i, keep=None):
             for j in range(BATCHES_PER_STEP):
-                pipe.submit(xs[(i * BATCHES_PER_STEP + j) % nbuf],
-                            copy_out=False)
+                t = pipe.submit(xs[(i * BATCHES_PER_STEP + j) % nbuf],
+                                copy_out=False)
+                if keep is not None:
+                    keep.append(t)
     else:
-        def step(i):
-            model(xs[i % nbuf].long()).argmax(dim=2).to("cpu")
+        def step(i, keep=None):
+            pred = model(xs[i % nbuf].long()).argmax(dim=2).to("cpu")
+            if keep is not None:
+                keep.append(pred)
 
     for i in range(args.warmup):
         step(i)
@@ -84,14 +106,32 @@ def bench_inference(args, rank, world, device):
         torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
+    # the last timed step keeps its tickets only when they are to be dumped
+    last = [] if args.dump_outputs else None
     t0 = time.perf_counter()
-    for i in range(args.steps):
+    for i in range(args.steps - 1):
         step(i)
+    if args.steps > 0:
+        step(args.steps - 1, last)
     if device.type == "cuda":
         torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
+
+    if last:
+        # copy_out=False leaves a slot's predictions valid until the slot is
+        # reused `depth` submissions later: the step's trailing `depth`
+        # batches are still intact after the sync
+        if pipe is not None:
+            last = [t() for t in last[-args.depth:]]
+        _dump(args, rank, "predictions", torch.stack(last))
+        # the timed path returns classes only (argmax is fused into the head
+        # kernel); one untimed forward of the step's final batch through the
+        # same model adds the logits behind them, a finer-grained comparison
+        with torch.no_grad():
+            logits = model(xs[(args.steps * BATCHES_PER_STEP - 1) % nbuf].long())
+        _dump(args, rank, "logits", logits)
 
     if world > 1:
         t = torch.tensor([elapsed], device=device if device.type == "cuda" else "cpu")
@@ -158,12 +198,15 @@ def bench_train(args, rank, world, device):
     if world > 1:
         torch.distributed.barrier()
     t0 = time.perf_counter()
+    loss = None
     for _ in range(args.steps):
-        fused_train_step(model, x, y, opt)
+        loss = fused_train_step(model, x, y, opt)
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and loss is not None:
+        _dump(args, rank, "train_loss", torch.as_tensor(loss).reshape(1))
     if world > 1:
         t = torch.tensor([elapsed], device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -214,17 +257,29 @@ def main():
     p.add_argument("--steps", type=int, default=400)
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--batch", type=int, default=C.BATCH_SIZE)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not "
+                        "need: the train section (--mode both)")
     p.add_argument("--mode", choices=["both", "inference", "train"],
-                   default="both",
-                   help="'both' (default) measures train windows/s first, "
-                        "then inference bases/s — the two halves of the "
-                        "BASELINE metric — and prints one JSON line each "
+                   default=None,
+                   help="default: 'inference' (the headline record only); "
+                        "with --full 'both', which measures train windows/s "
+                        "first, then inference bases/s — the two halves of "
+                        "the BASELINE metric — and prints one JSON line each "
                         "(inference last)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path "
+                        "returned in its last step as DIR/<name>.npy "
+                        "(float32): predictions (batches, batch, 90) for "
+                        "inference plus the logits (batch, 90, 5) of its "
+                        "final batch, train_loss for train")
     p.add_argument("--depth", type=int, default=48,
                    help="in-flight batches / HIP streams (inference mode); kept "
                         "below the default warmup so every hipGraph capture "
                         "happens untimed")
     args = p.parse_args()
+    if args.mode is None:
+        args.mode = "both" if args.full else "inference"
 
     rank, local_rank, world = init_distributed()
     if args.gpus != world:

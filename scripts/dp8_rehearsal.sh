@@ -6,7 +6,7 @@
 # Covers, in order:
 #   1. RCCL sanity: tiny all-reduce across N ranks (isolates comm stack
 #      issues from framework issues)
-#   2. bench.py --mode both at N ranks: DP train (FusedAdam flat
+#   2. bench.py --full (both modes) at N ranks: DP train (FusedAdam flat
 #      all-reduce per step) + weak-scaling inference
 #   3. torchrun roko_amd.train on synthetic windows: the CLI path with
 #      DistributedSampler + sharded validation
@@ -32,7 +32,7 @@ dist.destroy_process_group()
 "
 
 echo "== 2/3 bench.py both modes, $N ranks =="
-$TR bench.py --gpus "$N" --steps 100 --warmup 20
+$TR bench.py --gpus "$N" --steps 100 --warmup 20 --full
 
 echo "== 3/3 train CLI, $N ranks, synthetic windows =="
 python - <<'EOF'
