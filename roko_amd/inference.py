@@ -137,6 +137,98 @@ def stitch_contig(draft: str, keys: np.ndarray, counts: np.ndarray) -> str:
     return draft[: pos[0]] + mid + draft[pos[-1] + 1 :]
 
 
+#: dense consensus arrays (DeviceVotes.consensus / dense_majority): one byte
+#: per column slot, slot = pos * SLOTS_PER_POS + ins
+SLOTS_PER_POS = C.MAX_INS + 1
+NO_VOTE = 0xFF
+
+
+def dense_majority(keys: np.ndarray, counts: np.ndarray,
+                   contig_len: int) -> np.ndarray:
+    """(keys, counts) vote table -> dense uint8 majority array of
+    contig_len * SLOTS_PER_POS slots: the majority class per voted slot
+    (ties to the smallest class id, as in stitch_contig), NO_VOTE elsewhere.
+    The CPU reference of the consensus kernel (ops/hip/votes.hip)."""
+    maj = np.full(contig_len * SLOTS_PER_POS, NO_VOTE, dtype=np.uint8)
+    if len(keys):
+        keys = np.asarray(keys, dtype=np.int64)
+        slot = (keys >> _KEY_SHIFT) * SLOTS_PER_POS \
+            + (keys & ((1 << _KEY_SHIFT) - 1))
+        maj[slot] = counts.argmax(axis=1).astype(np.uint8)
+    return maj
+
+
+_BASE_BYTES = np.frombuffer(
+    C.LABEL_ALPHABET[: C.NUM_CLASSES].encode("ascii"), dtype=np.uint8)
+
+
+def stitch_dense(draft: str, maj: np.ndarray) -> str:
+    """stitch_contig over a dense majority array (see dense_majority): the
+    voted slots in slot order are exactly the sorted vote-table keys, so the
+    same four steps apply — drop leading insertion-only columns, draft
+    prefix, majority base per voted column skipping GAP, draft suffix."""
+    voted = np.flatnonzero(maj != NO_VOTE)
+    if len(voted) == 0:
+        return draft
+    on_pos = np.flatnonzero(voted % SLOTS_PER_POS == 0)
+    if len(on_pos) == 0:
+        return draft
+    voted = voted[on_pos[0]:]
+    m = maj[voted]
+    mid = _BASE_BYTES[m[m != C.LABEL_GAP]].tobytes().decode("ascii")
+    first = int(voted[0]) // SLOTS_PER_POS
+    last = int(voted[-1]) // SLOTS_PER_POS
+    return draft[:first] + mid + draft[last + 1:]
+
+
+def _infer_device_votes(rkw, dl, model, batch_size, depth, meter):
+    """RKW windows -> DeviceVotes: predictions and vote tables stay on the
+    GPU; returns ({contig: polished}, windows). Positions are fetched per
+    batch from the mmap in runs of one window group."""
+    from .ops.forward import InferencePipeline
+    from .ops.votes import DeviceVotes
+
+    lens = {c["name"]: int(c["len"]) for c in rkw.meta["contigs"]}
+    pipe = InferencePipeline(model, batch_size, depth=depth)
+    dv = DeviceVotes(lens, pipe)
+    group_contig = [g["contig"] for g in rkw.groups]
+    n_windows = 0
+    for gis, js, x in dl:
+        gis, js, x = gis.numpy(), js.numpy(), x.numpy()
+        # runs of one group (hence one contig, consecutive window offsets)
+        cuts = np.flatnonzero(np.diff(gis)) + 1
+        starts = np.concatenate([[0], cuts])
+        ends = np.concatenate([cuts, [len(gis)]])
+        # a slot batch votes into one contig's table: split at contig changes
+        lo = 0
+        while lo < len(starts):
+            contig = group_contig[int(gis[starts[lo]])]
+            hi = lo
+            while hi < len(starts) and \
+                    group_contig[int(gis[starts[hi]])] == contig:
+                hi += 1
+            a, b = int(starts[lo]), int(ends[hi - 1])
+            xs, ps = dv.staging()
+            xs[: b - a] = x[a:b]
+            for r in range(lo, hi):
+                _, pos_arr, _, _ = rkw.group_arrays(int(gis[starts[r]]))
+                s, e = int(starts[r]), int(ends[r])
+                ps[s - a : e - a] = pos_arr[int(js[s]) : int(js[e - 1]) + 1]
+            dv.add_batch(contig, b - a)
+            lo = hi
+        n_windows += len(gis)
+        meter.add(windows=len(gis), bases=len(gis) * C.WINDOW_STRIDE)
+    out: Dict[str, str] = {}
+    for name in rkw.contig_names():
+        draft = rkw.contig_seq(name)
+        if dv.has_votes(name):
+            out[name] = stitch_dense(draft, dv.consensus(name))
+            dv.free(name)
+        else:
+            out[name] = draft
+    return out, n_windows
+
+
 def infer(
     data_path: str,
     model_path: str,
@@ -146,6 +238,8 @@ def infer(
     device: Optional[torch.device] = None,
     model: Optional[RokoModel] = None,
     log=print,
+    votes: str = "host",
+    depth: int = 48,
 ) -> Dict[str, str]:
     """Polish the draft in `data_path` (RKW inference file) and return
     {contig: polished sequence}. Writes FASTA if `out_path` is given.
@@ -153,8 +247,17 @@ def infer(
     Under torchrun (WORLD_SIZE > 1) the window groups are sharded across
     ranks round-robin and partial vote tables gathered to rank 0; only rank 0
     returns sequences / writes the FASTA.
+
+    votes="device" keeps predictions and vote tables on the GPU
+    (ops/votes.py); single process, GPU only. `depth` is the number of
+    in-flight batches of the GPU pipeline.
     """
+    if votes not in ("host", "device"):
+        raise ValueError(f"votes must be 'host' or 'device', got {votes!r}")
     rank, local_rank, world = init_distributed()
+    if votes == "device" and world > 1:
+        raise ValueError("votes='device' is single-process only "
+                         f"(WORLD_SIZE={world}); use votes='host'")
     if device is None:
         device = (
             torch.device("cuda", local_rank)
@@ -165,6 +268,9 @@ def infer(
     if model is None:
         model = RokoModel()
         model.load_reference_checkpoint(model_path)
+    if votes == "device" and device.type != "cuda":
+        raise RuntimeError("votes='device' needs a ROCm GPU (the vote tables "
+                           "live in device memory); use votes='host'")
     model = model.to(device).eval()
 
     rkw = RkwFile(data_path)
@@ -185,12 +291,16 @@ def infer(
     n_windows = 0
     meter = Meter("inference", rank=rank)
     pipe = None
-    if device.type == "cuda":
+    out: Optional[Dict[str, str]] = None
+    if device.type == "cuda" and votes == "host":
         from .ops.forward import InferencePipeline
 
-        pipe = InferencePipeline(model, batch_size, depth=48)
+        pipe = InferencePipeline(model, batch_size, depth=depth)
     with torch.no_grad():
-        if pipe is not None:
+        if votes == "device":
+            out, n_windows = _infer_device_votes(rkw, dl, model, batch_size,
+                                                 depth, meter)
+        elif pipe is not None:
             # pipelined: keep `depth` batches in flight; votes are harvested
             # one pipeline-depth behind submission
             pending: List[tuple] = []
@@ -221,11 +331,17 @@ def infer(
         f"({bases / max(dt, 1e-9):.0f} bases/s)"
     )
 
-    votes: VoteTable = sv.finalize()
+    if out is not None:
+        if out_path:
+            write_fasta(out_path, sorted(out.items()))
+            log(f"wrote {len(out)} polished contigs to {out_path}")
+        return out
+
+    tables: VoteTable = sv.finalize()
 
     if world > 1:
         gathered: List[Optional[VoteTable]] = [None] * world if rank == 0 else None
-        dist.gather_object(votes, gathered, dst=0)
+        dist.gather_object(tables, gathered, dst=0)
         if rank != 0:
             return {}
         merged: VoteTable = {}
@@ -234,13 +350,13 @@ def infer(
             names.update(t.keys())
         for name in names:
             merged[name] = merge_votes([t[name] for t in gathered if name in t])
-        votes = merged
+        tables = merged
 
-    out: Dict[str, str] = {}
+    out = {}
     for name in rkw.contig_names():
         draft = rkw.contig_seq(name)
-        if name in votes:
-            out[name] = stitch_contig(draft, *votes[name])
+        if name in tables:
+            out[name] = stitch_contig(draft, *tables[name])
         else:
             out[name] = draft
     if out_path:

@@ -188,6 +188,27 @@ class InferencePipeline:
         self._next += 1
         return slot.submit(x, copy_out)
 
+    # -- votes mode: predictions stay on the GPU and vote into a device table
+    # (ops/votes.py DeviceVotes drives these three) -------------------------
+    def votes_staging(self):
+        """Pinned staging of the slot the next submit_votes() uses, as numpy
+        views x (batch, R, W) u8 and pos (batch, W, 2) i32. The slot is
+        synced first: its previous submit read this staging asynchronously."""
+        return self.slots[self._next % self.depth].votes_staging()
+
+    def submit_votes(self, n: int, table: torch.Tensor, n_slots: int,
+                     err_flag: torch.Tensor) -> None:
+        """Enqueue rows 0..n of the current staging: H2D, model, and one vote
+        per column into `table`. No predictions come back."""
+        slot = self.slots[self._next % self.depth]
+        self._next += 1
+        slot.submit_votes(n, table, n_slots, err_flag)
+
+    def drain(self) -> None:
+        """Wait for every slot; after this all submitted votes are in."""
+        for slot in self.slots:
+            slot.wait_done()
+
 
 class _Ticket:
     """Handle for one submitted batch; call it to wait and get the (n, W)
@@ -265,6 +286,30 @@ class _Slot:
             self.cpp.sync()
         else:
             self.event.synchronize()
+
+    def votes_staging(self):
+        if self.cpp is None:
+            raise RuntimeError(
+                "votes mode needs the C++ serving slot (ext.ServeSlot); it is "
+                "not available with ROKO_SERVE=graph or use_graphs=False")
+        if self.pending is not None:
+            self.pending.materialize()
+            self.pending = None
+        self.wait_done()
+        if getattr(self, "x_stage", None) is None:
+            b = self.host_out.shape[0]
+            self.x_stage = torch.zeros(
+                (b, C.WINDOW_ROWS, C.WINDOW_COLS), dtype=torch.uint8,
+                pin_memory=True)
+            self.pos_stage = torch.zeros(
+                (b, C.WINDOW_COLS, 2), dtype=torch.int32, pin_memory=True)
+        return self.x_stage.numpy(), self.pos_stage.numpy()
+
+    def submit_votes(self, n: int, table, n_slots: int, err_flag):
+        if getattr(self, "x_stage", None) is None:
+            raise RuntimeError("call votes_staging() and fill it first")
+        self.cpp.submit_votes(self.x_stage, self.pos_stage, n, table,
+                              n_slots, err_flag)
 
     def submit(self, x: torch.Tensor, copy_out: bool):
         n = x.shape[0]

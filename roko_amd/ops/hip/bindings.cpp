@@ -76,6 +76,11 @@ void front_de(const uint8_t* ids, const void* dt1g, const void* w1t_g,
               float* de, int B, uint32_t seed, float keep, hipStream_t stream,
               unsigned long long* timing, uint32_t dbg,
               const uint32_t* seed_ptr);
+void vote_scatter(const uint8_t* preds, const int32_t* positions,
+                  uint32_t* table, int64_t n_slots, uint32_t* err_flag,
+                  int n_cols, hipStream_t stream);
+void vote_consensus(const uint32_t* table, int64_t n_slots, uint8_t* maj,
+                    hipStream_t stream);
 }  // namespace rk
 
 namespace {
@@ -585,6 +590,54 @@ torch::Tensor atb_splitk(torch::Tensor A, torch::Tensor B) {
 }
 
 // ---------------------------------------------------------------------------
+// Device votes (votes.hip). The packed table and the error flag are int32
+// tensors on the Python side (torch has no first-class uint32); the kernels
+// treat the same bits as uint32.
+void check_launch(const char* what) {
+    hipError_t e = hipGetLastError();
+    TORCH_CHECK(e == hipSuccess, what, " launch: ", hipGetErrorString(e));
+}
+
+uint32_t* vote_table_ptr(const torch::Tensor& table, int64_t n_slots) {
+    check(table, torch::kInt32, "table");
+    TORCH_CHECK(n_slots >= 0 && n_slots <= table.numel(),
+                "n_slots exceeds the vote table");
+    return reinterpret_cast<uint32_t*>(table.data_ptr<int32_t>());
+}
+
+uint32_t* vote_err_ptr(const torch::Tensor& err_flag) {
+    check(err_flag, torch::kInt32, "err_flag");
+    TORCH_CHECK(err_flag.numel() == 1, "err_flag must hold one int32");
+    return reinterpret_cast<uint32_t*>(err_flag.data_ptr<int32_t>());
+}
+
+// preds (B, 90) u8 + positions (B, 90, 2) i32 -> one vote per column with
+// pos >= 0 added into `table`
+void vote_scatter(torch::Tensor preds, torch::Tensor positions,
+                  torch::Tensor table, int64_t n_slots,
+                  torch::Tensor err_flag) {
+    check(preds, torch::kUInt8, "preds");
+    check(positions, torch::kInt32, "positions");
+    TORCH_CHECK(positions.dim() >= 1 && positions.size(-1) == 2 &&
+                    positions.numel() == 2 * preds.numel(),
+                "positions must be preds.shape + (2,)");
+    TORCH_CHECK(preds.numel() < (int64_t(1) << 31), "batch too large");
+    rk::vote_scatter(preds.data_ptr<uint8_t>(), positions.data_ptr<int32_t>(),
+                     vote_table_ptr(table, n_slots), n_slots,
+                     vote_err_ptr(err_flag), (int)preds.numel(), cur_stream());
+    check_launch("vote kernel");
+}
+
+// table -> maj (n_slots) u8: majority class per slot, 0xFF where no votes
+void vote_consensus(torch::Tensor table, int64_t n_slots, torch::Tensor maj) {
+    check(maj, torch::kUInt8, "maj");
+    TORCH_CHECK(maj.numel() >= n_slots, "maj shorter than n_slots");
+    rk::vote_consensus(vote_table_ptr(table, n_slots), n_slots,
+                       maj.data_ptr<uint8_t>(), cur_stream());
+    check_launch("vote kernel");
+}
+
+// ---------------------------------------------------------------------------
 // Serving fast path: ONE C++ call enqueues the whole b-batch inference
 // forward on a slot-owned HIP stream.
 //
@@ -646,6 +699,14 @@ struct ServeSlot {
     hipGraph_t slot_graph = nullptr;
     hipGraphExec_t slot_gexec = nullptr;
     int n_runs = 0;
+    // votes mode (submit_votes): per-slot positions buffer, allocated on
+    // first use, and a second captured graph of the model body WITHOUT the
+    // prediction D2H — the vote scatter runs after it, outside the graph,
+    // because its table pointer changes per contig
+    torch::Tensor pos_buf;  // (B, 90, 2) i32
+    hipGraph_t votes_graph = nullptr;
+    hipGraphExec_t votes_gexec = nullptr;
+    bool votes_capture_failed = false;
 
     ServeSlot(py::dict w, int B_, torch::Tensor host_out_)
         : B(B_), stream(at::cuda::getStreamFromPool(/*high_priority=*/false)) {
@@ -698,6 +759,8 @@ struct ServeSlot {
     ~ServeSlot() {
         if (slot_gexec) (void)hipGraphExecDestroy(slot_gexec);
         if (slot_graph) (void)hipGraphDestroy(slot_graph);
+        if (votes_gexec) (void)hipGraphExecDestroy(votes_gexec);
+        if (votes_graph) (void)hipGraphDestroy(votes_graph);
         if (ev_in) (void)hipEventDestroy(ev_in);
         if (ev_done) (void)hipEventDestroy(ev_done);
     }
@@ -749,26 +812,63 @@ struct ServeSlot {
                      nullptr, amax.data_ptr<uint8_t>(), 90, B, s);
     }
 
-    void try_capture(hipStream_t s) {
+    // capture the model body (plus the prediction D2H when `d2h`) into
+    // graph/gexec; false (both left null) if any step fails
+    bool capture(hipStream_t s, bool d2h, hipGraph_t& graph,
+                 hipGraphExec_t& gexec) {
         hipError_t e =
             hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-        if (e != hipSuccess) { use_gslot = false; return; }
+        if (e != hipSuccess) return false;
         enqueue_model(s);
-        (void)hipMemcpyAsync(host_out.data_ptr(), amax.data_ptr(),
-                             (size_t)B * 90, hipMemcpyDeviceToHost, s);
-        e = hipStreamEndCapture(s, &slot_graph);
-        if (e != hipSuccess || !slot_graph) {
-            use_gslot = false;
-            slot_graph = nullptr;
-            return;
+        if (d2h)
+            (void)hipMemcpyAsync(host_out.data_ptr(), amax.data_ptr(),
+                                 (size_t)B * 90, hipMemcpyDeviceToHost, s);
+        e = hipStreamEndCapture(s, &graph);
+        if (e != hipSuccess || !graph) {
+            graph = nullptr;
+            return false;
         }
-        e = hipGraphInstantiate(&slot_gexec, slot_graph, nullptr, nullptr, 0);
+        e = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
         if (e != hipSuccess) {
-            (void)hipGraphDestroy(slot_graph);
-            slot_graph = nullptr;
-            slot_gexec = nullptr;
-            use_gslot = false;
+            (void)hipGraphDestroy(graph);
+            graph = nullptr;
+            gexec = nullptr;
+            return false;
         }
+        return true;
+    }
+
+    void try_capture(hipStream_t s) {
+        if (!capture(s, true, slot_graph, slot_gexec)) use_gslot = false;
+    }
+
+    // the hipBLASLt model body (slot batches the specialised xg GEMM does
+    // not cover): front -> 3x(addmm + GRU) -> head. The caller holds a
+    // CUDAStreamGuard on the slot stream for addmm_out.
+    void enqueue_model_lt(hipStream_t s) {
+        if (w1gt.defined() && use_v3)
+            rk::embed_mlp_fwd3(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
+                               b1.data_ptr<float>(), w2.data_ptr(),
+                               b2.data_ptr<float>(), emb.data_ptr(),
+                               seq.data_ptr(), B, s, nullptr);
+        else if (w1gt.defined())
+            rk::embed_mlp_fwd2(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
+                               b1.data_ptr<float>(), w2.data_ptr(),
+                               b2.data_ptr<float>(), emb.data_ptr(),
+                               seq.data_ptr(), B, s);
+        else
+            rk::embed_mlp_fwd(x_buf.data_ptr<uint8_t>(), w1.data_ptr(),
+                              b1.data_ptr<float>(), w2.data_ptr(),
+                              b2.data_ptr<float>(), emb.data_ptr(),
+                              seq.data_ptr(), B, s, 0, nullptr);
+        for (int l = 0; l < 3; ++l) {
+            at::addmm_out(xg2d, b_ih[l], l == 0 ? seq2d : hseq2d, w_ih_t[l]);
+            rk::gru_layer_fwd(xg.data_ptr(), u[l].data_ptr(),
+                              bhh[l].data_ptr<float>(), hseq.data_ptr(),
+                              nullptr, 90, B, s, 0);
+        }
+        rk::head_fwd(hseq.data_ptr(), w4.data_ptr(), b4.data_ptr<float>(),
+                     nullptr, amax.data_ptr<uint8_t>(), 90, B, s);
     }
 
     void run(torch::Tensor x, int64_t n) {
@@ -813,30 +913,7 @@ struct ServeSlot {
             at::cuda::CUDAStreamGuard guard(stream);
             hipStream_t s = stream.stream();
             if (n > 0) x_buf.narrow(0, 0, n).copy_(x.narrow(0, 0, n), true);
-            if (w1gt.defined() && use_v3)
-                rk::embed_mlp_fwd3(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
-                                   b1.data_ptr<float>(), w2.data_ptr(),
-                                   b2.data_ptr<float>(), emb.data_ptr(),
-                                   seq.data_ptr(), B, s, nullptr);
-            else if (w1gt.defined())
-                rk::embed_mlp_fwd2(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
-                                   b1.data_ptr<float>(), w2.data_ptr(),
-                                   b2.data_ptr<float>(), emb.data_ptr(),
-                                   seq.data_ptr(), B, s);
-            else
-                rk::embed_mlp_fwd(x_buf.data_ptr<uint8_t>(), w1.data_ptr(),
-                                  b1.data_ptr<float>(), w2.data_ptr(),
-                                  b2.data_ptr<float>(), emb.data_ptr(),
-                                  seq.data_ptr(), B, s, 0, nullptr);
-            for (int l = 0; l < 3; ++l) {
-                at::addmm_out(xg2d, b_ih[l], l == 0 ? seq2d : hseq2d,
-                              w_ih_t[l]);
-                rk::gru_layer_fwd(xg.data_ptr(), u[l].data_ptr(),
-                                  bhh[l].data_ptr<float>(), hseq.data_ptr(),
-                                  nullptr, 90, B, s, 0);
-            }
-            rk::head_fwd(hseq.data_ptr(), w4.data_ptr(), b4.data_ptr<float>(),
-                         nullptr, amax.data_ptr<uint8_t>(), 90, B, s);
+            enqueue_model_lt(s);
             host_out.copy_(amax, true);
         }
         (void)hipEventRecord(ev_done, stream.stream());
@@ -859,6 +936,69 @@ struct ServeSlot {
         run(std::move(x), n);
     }
     bool done() { return hipEventQuery(ev_done) == hipSuccess; }
+
+    // Votes mode: H2D of x and pos, the model, then one vote per column of
+    // rows 0..n added into `table` — all on the slot stream, and no D2H of
+    // predictions. Rows n..B of x_buf still hold the previous tenant, so the
+    // model does predict for them; they are kept from voting by pos = -1 in
+    // the positions buffer (data, not a launch scalar, so the same route
+    // serves the captured-graph and the eager body). All slots add into one
+    // table from their own streams; the adds are atomic. The caller keeps
+    // x/pos (pinned staging) untouched until sync(), and waits for every
+    // slot's ev_done before reading the table.
+    void submit_votes(torch::Tensor x, torch::Tensor pos, int64_t n,
+                      torch::Tensor table, int64_t n_slots,
+                      torch::Tensor err_flag) {
+        TORCH_CHECK(x.scalar_type() == torch::kUInt8 && x.is_contiguous() &&
+                        n >= 0 && n <= B && x.numel() >= n * 200 * 90,
+                    "x must be contiguous u8 with n <= slot batch rows");
+        TORCH_CHECK(pos.scalar_type() == torch::kInt32 && pos.is_contiguous()
+                        && pos.numel() >= n * 180,
+                    "pos must be contiguous i32 (>=n, 90, 2)");
+        uint32_t* tab = vote_table_ptr(table, n_slots);
+        uint32_t* err = vote_err_ptr(err_flag);
+        if (!pos_buf.defined())
+            pos_buf = torch::empty({B, 90, 2},
+                                   x_buf.options().dtype(torch::kInt32));
+        // order the slot stream behind the producer of x/pos and of the
+        // table's zero fill
+        auto prod = at::cuda::getCurrentCUDAStream();
+        (void)hipEventRecord(ev_in, prod.stream());
+        (void)hipStreamWaitEvent(stream.stream(), ev_in, 0);
+        for (const torch::Tensor* t : {&x, &pos, &table, &err_flag})
+            if (t->is_cuda())
+                c10::cuda::CUDACachingAllocator::recordStream(
+                    t->storage().data_ptr(), stream);
+        at::cuda::CUDAStreamGuard guard(stream);
+        hipStream_t s = stream.stream();
+        if (n > 0) {
+            (void)hipMemcpyAsync(x_buf.data_ptr(), x.data_ptr(),
+                                 (size_t)n * 200 * 90, hipMemcpyDefault, s);
+            (void)hipMemcpyAsync(pos_buf.data_ptr(), pos.data_ptr(),
+                                 (size_t)n * 180 * sizeof(int32_t),
+                                 hipMemcpyDefault, s);
+        }
+        if (n < B)  // every byte 0xFF -> pos = ins = -1: the row does not vote
+            (void)hipMemsetAsync(pos_buf.data_ptr<int32_t>() + n * 180, 0xFF,
+                                 (size_t)(B - n) * 180 * sizeof(int32_t), s);
+        if (use_fold || xg2_path) {
+            if (use_gslot && !votes_gexec && !votes_capture_failed &&
+                n_runs >= 1)
+                votes_capture_failed =
+                    !capture(s, false, votes_graph, votes_gexec);
+            if (votes_gexec)
+                (void)hipGraphLaunch(votes_gexec, s);
+            else
+                enqueue_model(s);
+        } else {
+            enqueue_model_lt(s);
+        }
+        rk::vote_scatter(amax.data_ptr<uint8_t>(),
+                         pos_buf.data_ptr<int32_t>(), tab, n_slots, err,
+                         B * 90, s);
+        ++n_runs;
+        (void)hipEventRecord(ev_done, stream.stream());
+    }
 };
 
 // Create a HIP stream restricted to all but the first `reserve_cus` CUs.
@@ -935,6 +1075,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("head_fwd", &head_fwd, py::arg("hseq"), py::arg("w4"), py::arg("b4"),
           py::arg("want_logits") = true, py::arg("want_argmax") = false);
     m.def("cu_masked_stream", &cu_masked_stream, py::arg("reserve_cus"));
+    m.def("vote_scatter", &vote_scatter, py::arg("preds"),
+          py::arg("positions"), py::arg("table"), py::arg("n_slots"),
+          py::arg("err_flag"));
+    m.def("vote_consensus", &vote_consensus, py::arg("table"),
+          py::arg("n_slots"), py::arg("maj"));
     py::class_<ServeSlot>(m, "ServeSlot")
         .def(py::init<py::dict, int, torch::Tensor>(), py::arg("weights"),
              py::arg("batch"), py::arg("host_out"))
@@ -944,5 +1089,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("sync", &ServeSlot::sync,
              py::call_guard<py::gil_scoped_release>())
         .def("done", &ServeSlot::done)
+        .def("submit_votes", &ServeSlot::submit_votes, py::arg("x"),
+             py::arg("pos"), py::arg("n"), py::arg("table"),
+             py::arg("n_slots"), py::arg("err_flag"),
+             py::call_guard<py::gil_scoped_release>())
+        .def_readonly("amax", &ServeSlot::amax)
         .def_readonly("host_out", &ServeSlot::host_out);
 }

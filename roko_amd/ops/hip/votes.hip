@@ -1,0 +1,105 @@
+// On-device majority vote (reference: inference.py:119-147 — the per-base
+// Counter loop + most_common). Predictions never leave the GPU: every
+// (window, column) adds one vote into a dense per-contig table, and the
+// consensus is a per-slot argmax of which only one byte per slot is copied
+// back (docs/KERNELS.md "Device votes").
+//
+// Table: one uint32 per column slot, slot = pos * (MAX_INS + 1) + ins, holding
+// five 4-bit class counters (class c in bits [4c, 4c+4)). A column receives at
+// most 6 votes from the extractor's window geometry, so 4 bits (max 15) hold
+// it; a 16th vote for one class is detected through the atomic's return value
+// and reported in err_flag, never silent.
+
+#include <cstdint>
+
+#include "common.h"
+
+namespace rk {
+
+constexpr int VOTE_CLASSES = 5;
+constexpr int VOTE_INS_SLOTS = 4;  // MAX_INS + 1
+constexpr uint32_t VOTE_ERR_RANGE = 1u;     // pos / ins / class out of range
+constexpr uint32_t VOTE_ERR_OVERFLOW = 2u;  // a 4-bit counter was already 15
+
+// One thread per (window, column). Rows with pos < 0 are padding and do not
+// vote. Integer adds commute, so the table is exact and reproducible whatever
+// the order the slots' streams arrive in; relaxed agent-scope atomics are
+// enough because the table is only read by a later kernel.
+__global__ __launch_bounds__(256) void vote_scatter_kernel(
+    const uint8_t* __restrict__ preds,  // (n_cols)
+    const int2* __restrict__ positions, // (n_cols) {pos, ins}
+    uint32_t* __restrict__ table,       // (n_slots)
+    int64_t n_slots, uint32_t* __restrict__ err_flag, int n_cols) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_cols) return;
+    const int2 p = positions[i];
+    if (p.x < 0) return;
+    const uint32_t cls = preds[i];
+    const int64_t slot = (int64_t)p.x * VOTE_INS_SLOTS + p.y;
+    if (p.y < 0 || p.y >= VOTE_INS_SLOTS || slot >= n_slots ||
+        cls >= VOTE_CLASSES) {
+        __hip_atomic_fetch_or(err_flag, VOTE_ERR_RANGE, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const uint32_t old = __hip_atomic_fetch_add(
+        &table[slot], 1u << (4 * cls), __ATOMIC_RELAXED,
+        __HIP_MEMORY_SCOPE_AGENT);
+    if (((old >> (4 * cls)) & 15u) == 15u)
+        __hip_atomic_fetch_or(err_flag, VOTE_ERR_OVERFLOW, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// majority class of one packed slot; ties -> smallest class id (the strict
+// '>' keeps the first maximum, as numpy's argmax does); no votes -> 0xFF
+RK_DEV uint32_t vote_majority(uint32_t v) {
+    if (v == 0u) return 0xFFu;
+    uint32_t best = 0, bc = v & 15u;
+#pragma unroll
+    for (uint32_t c = 1; c < VOTE_CLASSES; ++c) {
+        const uint32_t n = (v >> (4 * c)) & 15u;
+        if (n > bc) { bc = n; best = c; }
+    }
+    return best;
+}
+
+// One thread per 4 slots: one 16-byte load, one packed 4-byte store (a wave
+// reads 1 KiB and writes 256 B, both contiguous). The last, partial group
+// goes slot by slot.
+__global__ __launch_bounds__(256) void vote_consensus_kernel(
+    const uint32_t* __restrict__ table, int64_t n_slots,
+    uint8_t* __restrict__ maj) {
+    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (s0 >= n_slots) return;
+    if (s0 + 4 <= n_slots) {
+        const uint4 v = *reinterpret_cast<const uint4*>(table + s0);
+        const uint32_t out = vote_majority(v.x) | (vote_majority(v.y) << 8) |
+                             (vote_majority(v.z) << 16) |
+                             (vote_majority(v.w) << 24);
+        *reinterpret_cast<uint32_t*>(maj + s0) = out;
+    } else {
+        for (int64_t s = s0; s < n_slots; ++s)
+            maj[s] = (uint8_t)vote_majority(table[s]);
+    }
+}
+
+void vote_scatter(const uint8_t* preds, const int32_t* positions,
+                  uint32_t* table, int64_t n_slots, uint32_t* err_flag,
+                  int n_cols, hipStream_t stream) {
+    if (n_cols <= 0) return;
+    hipLaunchKernelGGL(vote_scatter_kernel, dim3((n_cols + 255) / 256),
+                       dim3(256), 0, stream, preds,
+                       reinterpret_cast<const int2*>(positions), table,
+                       n_slots, err_flag, n_cols);
+}
+
+void vote_consensus(const uint32_t* table, int64_t n_slots, uint8_t* maj,
+                    hipStream_t stream) {
+    if (n_slots <= 0) return;
+    const int64_t groups = (n_slots + 3) / 4;
+    hipLaunchKernelGGL(vote_consensus_kernel,
+                       dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
+                       stream, table, n_slots, maj);
+}
+
+}  // namespace rk

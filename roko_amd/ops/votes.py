@@ -1,0 +1,161 @@
+"""Device-resident majority vote (kernels: ops/hip/votes.hip).
+
+The host vote path brings every prediction over PCIe and folds it into
+(keys, counts) tables with numpy group-bys. Here the predictions never leave
+the GPU: each serving slot adds its batch's votes into a dense per-contig
+table in device memory, and only the per-slot majority — one byte — is
+copied back, once per contig.
+
+Table layout: one 32-bit word per column slot, slot = pos * (MAX_INS + 1) +
+ins, five 4-bit class counters per word (16 B per draft base). The window
+extractor gives a column at most 6 votes (docs/KERNELS.md), so 4 bits hold
+it; a counter that would pass 15 sets an error flag and `counts()` /
+`consensus()` raise instead of returning a corrupted table.
+"""
+
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .. import config as C
+
+SLOTS_PER_POS = C.MAX_INS + 1
+_KEY_SHIFT = 3  # VoteTable key = pos << 3 | ins (inference.py)
+_NIBBLE = 4
+_ERR_RANGE = 1
+_ERR_OVERFLOW = 2
+
+
+class VoteOverflowError(RuntimeError):
+    """A column received more votes for one class than a 4-bit counter
+    holds; the device table is not usable."""
+
+
+class DeviceVotes:
+    """Per-contig vote tables in device memory.
+
+    `contig_lens` maps contig name -> draft length. Tables are allocated
+    zeroed on a contig's first batch and released by `free()`. With a
+    `pipe` (ops.forward.InferencePipeline) batches go through its serving
+    slots in votes mode: fill `staging()`, then `add_batch(contig, n)`.
+    `scatter()` adds given predictions directly (tests, merging).
+    """
+
+    def __init__(self, contig_lens: Dict[str, int], pipe=None,
+                 device: Optional[torch.device] = None):
+        from . import ext
+
+        self.ext = ext()
+        self.lens = dict(contig_lens)
+        self.pipe = pipe
+        if device is None:
+            device = (next(pipe.model.parameters()).device if pipe is not None
+                      else torch.device("cuda", torch.cuda.current_device()))
+        self.device = device
+        self.tables: Dict[str, torch.Tensor] = {}
+        self.err_flag = torch.zeros(1, dtype=torch.int32, device=device)
+        self._stage = None
+
+    # -- tables --------------------------------------------------------------
+    def n_slots(self, contig: str) -> int:
+        return self.lens[contig] * SLOTS_PER_POS
+
+    def table(self, contig: str) -> torch.Tensor:
+        t = self.tables.get(contig)
+        if t is None:
+            t = torch.zeros(self.n_slots(contig), dtype=torch.int32,
+                            device=self.device)
+            self.tables[contig] = t
+        return t
+
+    def has_votes(self, contig: str) -> bool:
+        return contig in self.tables
+
+    def free(self, contig: str) -> None:
+        self.drain()
+        self.tables.pop(contig, None)
+
+    def _validate(self, contig: str, positions: np.ndarray) -> None:
+        """Host-side range check before anything is uploaded; the kernel's
+        own guard is only the second line of defence."""
+        if positions.size == 0:
+            return
+        p, i = positions[..., 0], positions[..., 1]
+        if p.min() < 0 or p.max() >= self.lens[contig]:
+            raise ValueError(
+                f"{contig}: window position outside [0, {self.lens[contig]})"
+                f" (min {int(p.min())}, max {int(p.max())})")
+        if i.min() < 0 or i.max() > C.MAX_INS:
+            raise ValueError(
+                f"{contig}: insertion slot outside [0, {C.MAX_INS}]"
+                f" (min {int(i.min())}, max {int(i.max())})")
+
+    # -- adding votes --------------------------------------------------------
+    def staging(self) -> Tuple[np.ndarray, np.ndarray]:
+        """Pinned (x, pos) staging of the next slot, safe to overwrite."""
+        self._stage = self.pipe.votes_staging()
+        return self._stage
+
+    def add_batch(self, contig: str, n: int) -> None:
+        """Submit rows 0..n of the staging last returned by `staging()`."""
+        if self._stage is None:
+            raise RuntimeError("fill staging() before add_batch()")
+        self._validate(contig, self._stage[1][:n])
+        self._stage = None
+        self.pipe.submit_votes(n, self.table(contig), self.n_slots(contig),
+                               self.err_flag)
+
+    def scatter(self, contig: str, preds, positions) -> None:
+        """Add given predictions (N, W) u8 at positions (N, W, 2) i32 on the
+        current stream. Rows with pos < 0 do not vote."""
+        positions = np.ascontiguousarray(positions, dtype=np.int32)
+        preds = np.ascontiguousarray(preds, dtype=np.uint8)
+        live = positions[positions[..., 0] >= 0]
+        self._validate(contig, live)
+        if preds.size and preds.max() >= C.NUM_CLASSES:
+            raise ValueError("prediction class outside [0, NUM_CLASSES)")
+        self.ext.vote_scatter(
+            torch.from_numpy(preds).to(self.device),
+            torch.from_numpy(positions).to(self.device),
+            self.table(contig), self.n_slots(contig), self.err_flag)
+
+    # -- reading -------------------------------------------------------------
+    def drain(self) -> None:
+        if self.pipe is not None:
+            self.pipe.drain()
+
+    def _check(self) -> None:
+        self.drain()
+        flag = int(self.err_flag.item())
+        if flag & _ERR_OVERFLOW:
+            raise VoteOverflowError(
+                "device vote table overflow: a column received more than 15 "
+                "votes for one class (4-bit counters); rerun with host votes "
+                "(votes='host')")
+        if flag & _ERR_RANGE:
+            raise RuntimeError(
+                "device vote kernel dropped an out-of-range position or "
+                "class; the table is incomplete — rerun with host votes")
+
+    def counts(self, contig: str) -> Tuple[np.ndarray, np.ndarray]:
+        """Unpack a table to the host VoteTable form: (keys int64 sorted,
+        counts int64 (K, NUM_CLASSES)), key = pos << 3 | ins."""
+        self._check()
+        tab = self.table(contig).cpu().numpy().view(np.uint32)
+        slots = np.flatnonzero(tab)
+        keys = ((slots // SLOTS_PER_POS) << _KEY_SHIFT) | (slots % SLOTS_PER_POS)
+        shifts = np.arange(C.NUM_CLASSES, dtype=np.uint32) * _NIBBLE
+        counts = (tab[slots, None] >> shifts[None, :]) & 15
+        return keys.astype(np.int64), counts.astype(np.int64)
+
+    def consensus(self, contig: str) -> np.ndarray:
+        """Majority class per slot (uint8, 0xFF = no votes), ties to the
+        smallest class id: one kernel and one D2H of a byte per slot."""
+        self._check()
+        n = self.n_slots(contig)
+        maj = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self.ext.vote_consensus(self.table(contig), n, maj)
+        return maj.cpu().numpy()

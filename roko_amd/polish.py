@@ -1,0 +1,274 @@
+"""One-command polish: draft FASTA + reads BAM + .pth -> polished FASTA.
+
+  python -m roko_amd.polish <draft.fasta> <reads.bam> <model.pth> <out.fasta>
+      [--t workers] [--b batch] [--seed N]
+
+Does what `features` followed by `inference` does, and writes the same FASTA
+byte for byte, without the RKW file between them: region windows stream from
+the extractor workers straight into the serving slots. On a GPU the majority
+vote happens on the device too (ops/votes.py) — predictions and vote tables
+never cross PCIe; one byte per column comes back per contig. Without a GPU
+the model's torch forward and the host vote tables are used, as in
+`inference.infer`.
+
+Single process only; for multi-GPU runs use `features` + `inference` under
+torchrun.
+"""
+
+from __future__ import annotations
+
+import argparse
+import multiprocessing
+import time
+from typing import Dict, List, Optional
+
+import numpy as np
+
+from . import config as C
+from .config import FeatureConfig
+from .features import generate_infer, generate_regions
+from .io.fasta import read_fasta, write_fasta
+
+# NOTE: torch (and everything that imports it) is imported inside polish():
+# spawned extractor workers re-import this module when it is the program's
+# main module, and must neither pay the torch import nor touch the GPU.
+
+
+#: figures of the last polish() call in this process (scripts/polish_bench.py)
+LAST_RUN: Dict[str, float] = {}
+
+
+class _DeviceSink:
+    """Windows -> serving slots in votes mode -> DeviceVotes. Region arrays
+    are packed into the slots' pinned staging with slice copies; a contig is
+    stitched from its consensus bytes as soon as its last region is in."""
+
+    def __init__(self, model, batch: int, depth: int, lens: Dict[str, int]):
+        from .ops.forward import InferencePipeline
+        from .ops.votes import DeviceVotes
+
+        self.batch = batch
+        self.dv = DeviceVotes(lens, InferencePipeline(model, batch,
+                                                      depth=depth))
+        self.x = self.pos = None
+        self.fill = 0
+
+    def add(self, contig: str, positions: np.ndarray,
+            examples: np.ndarray) -> None:
+        n, off = len(positions), 0
+        while off < n:
+            if self.fill == 0:
+                # syncs the slot that owns this staging pair before reuse
+                self.x, self.pos = self.dv.staging()
+            k = min(self.batch - self.fill, n - off)
+            self.x[self.fill : self.fill + k] = examples[off : off + k]
+            self.pos[self.fill : self.fill + k] = positions[off : off + k]
+            self.fill += k
+            off += k
+            if self.fill == self.batch:
+                self._submit(contig)
+
+    def _submit(self, contig: str) -> None:
+        self.dv.add_batch(contig, self.fill)
+        self.fill = 0
+
+    def finish_contig(self, contig: str, draft: str) -> Optional[str]:
+        from .inference import stitch_dense
+
+        if self.fill:
+            self._submit(contig)  # a slot batch votes into one contig's table
+        if not self.dv.has_votes(contig):
+            return draft
+        maj = self.dv.consensus(contig)  # drains the pipeline first
+        self.dv.free(contig)
+        return stitch_dense(draft, maj)
+
+    def finish(self) -> Dict[str, str]:
+        return {}
+
+
+class _HostSink:
+    """CPU route: the model's torch forward + host vote tables, batched
+    exactly as `infer` batches an RKW file (consecutive windows in job order,
+    across contig boundaries), so both routes run the model on identical
+    batches. Contigs are stitched at the end."""
+
+    def __init__(self, model, batch: int, device, drafts: Dict[str, str]):
+        from .inference import StreamingVotes
+
+        self.model, self.batch, self.device = model, batch, device
+        self.drafts = drafts
+        self.sv = StreamingVotes()
+        self.buf: List[tuple] = []  # (contig, positions, examples) chunks
+        self.n = 0
+
+    def add(self, contig, positions, examples) -> None:
+        if len(positions):
+            self.buf.append((contig, positions, examples))
+            self.n += len(positions)
+        while self.n >= self.batch:
+            self._run(self.batch)
+
+    def _run(self, k: int) -> None:
+        import torch
+
+        take, rest, got = [], [], 0
+        for contig, p, x in self.buf:
+            m = min(len(p), k - got)
+            if m:
+                take.append((contig, p[:m], x[:m]))
+                got += m
+            if m < len(p):
+                rest.append((contig, p[m:], x[m:]))
+        self.buf, self.n = rest, self.n - got
+        x = torch.from_numpy(np.concatenate([t[2] for t in take]))
+        with torch.no_grad():
+            logits = self.model(x.to(self.device).long())
+        preds = logits.argmax(dim=2).to(torch.uint8).cpu().numpy()
+        row = 0
+        for contig, p, _ in take:
+            for j in range(len(p)):  # StreamingVotes takes single windows
+                self.sv.add(contig, np.asarray(p[j]), preds[row + j])
+            row += len(p)
+
+    def finish_contig(self, contig: str, draft: str) -> Optional[str]:
+        return None  # stitched in finish()
+
+    def finish(self) -> Dict[str, str]:
+        from .inference import stitch_contig
+
+        if self.n:
+            self._run(self.n)
+        tables = self.sv.finalize()
+        return {name: stitch_contig(self.drafts[name], *tables[name])
+                for name in tables}
+
+
+def polish(
+    draft_fasta: str,
+    reads_bam: str,
+    model_path: Optional[str],
+    out_fasta: Optional[str],
+    workers: int = 1,
+    batch_size: int = C.BATCH_SIZE,
+    cfg: Optional[FeatureConfig] = None,
+    device=None,
+    model=None,
+    log=print,
+    depth: int = 16,
+) -> Dict[str, str]:
+    """Polish `draft_fasta` with the reads in `reads_bam`; returns {contig:
+    polished sequence} and writes FASTA if `out_fasta` is given. Regions,
+    FeatureConfig and seeding are those of `features.run`; `depth` is the
+    number of in-flight batches on the GPU."""
+    cfg = cfg or FeatureConfig()
+    refs = list(read_fasta(draft_fasta))
+    jobs = []
+    for name, seq in refs:
+        for start, end in generate_regions(len(seq), cfg.region_size,
+                                           cfg.region_overlap):
+            jobs.append((reads_bam, name, start, end, cfg))
+
+    # Start the extractor workers first, in fresh interpreters: forking a
+    # process that has initialised HIP is unsafe (and the caller may have
+    # done so already), and only this process may hold the GPU.
+    pool = None
+    if workers > 1 and jobs:
+        pool = multiprocessing.get_context("spawn").Pool(processes=workers)
+    try:
+        return _polish(refs, jobs, pool, model_path, out_fasta, workers,
+                       batch_size, device, model, log, depth)
+    finally:
+        if pool is not None:
+            pool.terminate()
+            pool.join()
+
+
+def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
+            device, model, log, depth) -> Dict[str, str]:
+    import torch
+
+    from .model import RokoModel
+
+    if device is None:
+        device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    device = torch.device(device)
+    if model is None:
+        model = RokoModel()
+        model.load_reference_checkpoint(model_path)
+    model = model.to(device).eval()
+
+    drafts = dict(refs)
+    if device.type == "cuda":
+        sink = _DeviceSink(model, batch_size, depth,
+                           {n: len(s) for n, s in refs})
+    else:
+        sink = _HostSink(model, batch_size, device, drafts)
+    log(f"polish: {len(jobs)} region jobs, {workers} workers, "
+        f"batch {batch_size}, votes on {device.type}")
+
+    out: Dict[str, str] = {}
+    n_windows = n_errors = 0
+    t0 = time.time()
+    results = (pool.imap(generate_infer, jobs) if pool is not None
+               else map(generate_infer, jobs))
+    current = None  # contig being consumed; jobs are in contig order
+    for result, job in zip(results, jobs):
+        contig = job[1]
+        if contig != current:
+            if current is not None:
+                seq = sink.finish_contig(current, drafts[current])
+                if seq is not None:
+                    out[current] = seq
+            current = contig
+        if result[0] == "__error__":
+            # same fence as features.run: one in-parent retry, then skip
+            log(f"WARNING: region {result[1]} failed: {result[2]} "
+                "(retrying once)")
+            result = generate_infer(job)
+            if result[0] == "__error__":
+                n_errors += 1
+                log(f"WARNING: region {result[1]} failed twice: "
+                    f"{result[2]} (skipped)")
+                continue
+        _, _, _, positions, examples, _ = result
+        sink.add(contig, positions, examples)
+        n_windows += len(positions)
+    if current is not None:
+        seq = sink.finish_contig(current, drafts[current])
+        if seq is not None:
+            out[current] = seq
+    out.update(sink.finish())
+    for name, seq in refs:  # contigs with no windows come out as the draft
+        out.setdefault(name, seq)
+
+    dt = time.time() - t0
+    log(f"polished {len(out)} contigs: {n_windows} windows in {dt:.1f}s "
+        f"({n_windows / max(dt, 1e-9):.0f} windows/s, "
+        f"{n_windows * C.WINDOW_STRIDE / max(dt, 1e-9):.0f} bases/s)"
+        + (f"; {n_errors} regions FAILED and were skipped" if n_errors
+           else ""))
+    LAST_RUN.update(windows=n_windows, seconds=dt, failed_regions=n_errors)
+    if out_fasta:
+        write_fasta(out_fasta, sorted(out.items()))
+        log(f"wrote {len(out)} polished contigs to {out_fasta}")
+    return out
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__)
+    p.add_argument("draft", help="draft assembly FASTA")
+    p.add_argument("bam", help="reads-to-draft BAM (indexed)")
+    p.add_argument("model", help=".pth checkpoint (reference format)")
+    p.add_argument("out", help="output FASTA path")
+    p.add_argument("--t", type=int, default=4,
+                   help="extractor worker processes (they never use the GPU)")
+    p.add_argument("--b", type=int, default=C.BATCH_SIZE, help="batch size")
+    p.add_argument("--seed", type=int, default=0)
+    a = p.parse_args(argv)
+    polish(a.draft, a.bam, a.model, a.out, workers=a.t, batch_size=a.b,
+           cfg=FeatureConfig(seed=a.seed))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,144 @@
+"""End-to-end polishing rate: draft + BAM -> FASTA, three ways.
+
+  python scripts/polish_bench.py [--ref-len N] [--cov C] [--t WORKERS]
+      [--b BATCH] [--limit SECONDS] [--dir DIR]
+
+Builds a synthetic assembly (the generators of tests/test_gpu_e2e.py::
+_make_case, size given by --ref-len), then times
+
+  two_step      features -> RKW file -> infer(votes="host")
+  infer_device  features -> RKW file -> infer(votes="device")
+  polish        roko_amd.polish.polish (no file, votes on the device)
+
+Each way runs in a process of its own under `timeout` (--limit seconds), so
+one that hangs or faults ends there and nothing is started after it. Each
+prints one JSON line: wall time, windows/s, bases/s (draft bases per second
+of wall time), and for the file routes the split between extraction and
+inference. A last line says whether the three FASTA files are identical.
+The model is randomly initialised: rates do not depend on the weights.
+"""
+
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+STEPS = ("two_step", "infer_device", "polish")
+
+
+def make_case(d, ref_len, cov, seed=7):
+    import numpy as np
+
+    from roko_amd.io.bamio import write_bam
+    from roko_amd.io.fasta import write_fasta
+    from tests.simple_align import BASES, EditScript
+
+    rng = np.random.default_rng(seed)
+    truth = "".join(BASES[int(b)] for b in rng.integers(0, 4, ref_len))
+    es = EditScript(rng, truth, sub_rate=0.01, ins_rate=0.003, del_rate=0.003)
+    write_fasta(os.path.join(d, "draft.fasta"), [("ctg1", es.draft)])
+    reads, rlen = [], 400
+    for i in range(max(1, cov * len(truth) // rlen)):
+        s = int(rng.integers(0, max(1, len(truth) - rlen)))
+        rec = es.align_substring(f"read{i}", s, s + rlen,
+                                 flag=16 if i % 2 else 0)
+        if rec is not None:
+            reads.append(rec)
+    reads.sort(key=lambda r: (r.tid, r.pos))
+    write_bam(os.path.join(d, "reads.bam"), [("ctg1", len(es.draft))], reads)
+    return len(es.draft)
+
+
+def run_step(step, d, workers, batch, region):
+    """One route, in this (child) process; prints its JSON line."""
+    from roko_amd import config as C
+    from roko_amd.config import FeatureConfig
+    from roko_amd.features import run as features_run
+    from roko_amd.inference import infer
+    from roko_amd.io.fasta import read_fasta
+    from roko_amd.polish import polish
+
+    quiet = lambda *a, **k: None  # noqa: E731
+    draft = os.path.join(d, "draft.fasta")
+    bam = os.path.join(d, "reads.bam")
+    ckpt = os.path.join(d, "model.pth")
+    out = os.path.join(d, f"{step}.fasta")
+    cfg = FeatureConfig(seed=1, region_size=region)
+    draft_bases = sum(len(s) for _, s in read_fasta(draft))
+    rec = {"step": step, "workers": workers, "batch": batch,
+           "draft_bases": draft_bases}
+    t0 = time.time()
+    if step == "polish":
+        from roko_amd.polish import LAST_RUN
+
+        polish(draft, bam, ckpt, out, workers=workers, batch_size=batch,
+               cfg=cfg, log=quiet)
+        n = LAST_RUN["windows"]
+    else:
+        rkw = os.path.join(d, f"{step}.rkw")
+        n = features_run(draft, bam, rkw, workers=workers, cfg=cfg, log=quiet)
+        rec["features_s"] = round(time.time() - t0, 3)
+        t1 = time.time()
+        infer(rkw, ckpt, out, batch_size=batch, log=quiet,
+              votes="host" if step == "two_step" else "device")
+        rec["infer_s"] = round(time.time() - t1, 3)
+    wall = time.time() - t0
+    rec.update(windows=n, wall_s=round(wall, 3),
+               windows_per_s=round(n / wall, 1),
+               bases_per_s=round(draft_bases / wall, 1),
+               window_bases_per_s=round(n * C.WINDOW_STRIDE / wall, 1))
+    print(json.dumps(rec), flush=True)
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__)
+    p.add_argument("--ref-len", type=int, default=200_000)
+    p.add_argument("--cov", type=int, default=25)
+    p.add_argument("--t", type=int, default=4, help="extractor workers")
+    p.add_argument("--b", type=int, default=128, help="batch size")
+    p.add_argument("--region", type=int, default=20_000,
+                   help="region size (the unit of extractor parallelism)")
+    p.add_argument("--limit", type=int, default=240,
+                   help="time limit per route, seconds")
+    p.add_argument("--dir", default=None, help="work directory")
+    p.add_argument("--step", choices=STEPS, default=None,
+                   help="(internal) run one route in this process")
+    a = p.parse_args()
+    if a.step:
+        run_step(a.step, a.dir, a.t, a.b, a.region)
+        return
+
+    import torch
+
+    from roko_amd.model import RokoModel
+
+    d = a.dir or tempfile.mkdtemp(prefix="polish_bench_")
+    os.makedirs(d, exist_ok=True)
+    t0 = time.time()
+    n = make_case(d, a.ref_len, a.cov)
+    torch.manual_seed(0)
+    torch.save(RokoModel().state_dict(), os.path.join(d, "model.pth"))
+    print(json.dumps({"step": "make_case", "draft_bases": n,
+                      "wall_s": round(time.time() - t0, 1)}), flush=True)
+    for step in STEPS:
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable,
+               os.path.abspath(__file__), "--step", step, "--dir", d,
+               "--t", str(a.t), "--b", str(a.b), "--region", str(a.region)]
+        rc = subprocess.call(cmd)
+        if rc != 0:
+            print(json.dumps({"step": step, "failed": rc}), flush=True)
+            sys.exit(rc)  # start nothing more after a failure
+    blobs = [open(os.path.join(d, f"{s}.fasta"), "rb").read() for s in STEPS]
+    print(json.dumps({"step": "compare",
+                      "identical": blobs[0] == blobs[1] == blobs[2]}),
+          flush=True)
+
+
+if __name__ == "__main__":
+    main()
