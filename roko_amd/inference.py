@@ -189,7 +189,8 @@ def _infer_device_votes(rkw, dl, model, batch_size, depth, meter):
     from .ops.votes import DeviceVotes
 
     lens = {c["name"]: int(c["len"]) for c in rkw.meta["contigs"]}
-    pipe = InferencePipeline(model, batch_size, depth=depth)
+    # votes mode runs one batch per slot (coalesce=1)
+    pipe = InferencePipeline(model, batch_size, depth=depth, coalesce=1)
     dv = DeviceVotes(lens, pipe)
     group_contig = [g["contig"] for g in rkw.groups]
     n_windows = 0

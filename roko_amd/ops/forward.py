@@ -124,6 +124,21 @@ def roko_forward(model, x: torch.Tensor) -> torch.Tensor:
     return logits[:B0]
 
 
+#: shipped coalescing request (ROKO_COALESCE overrides): consecutive
+#: submits that share one wide slot. Chosen by the sweep recorded in
+#: profiles/PERF_HISTORY.md ("Cross-batch coalescing").
+_COALESCE_DEFAULT = 8
+
+
+def coalesce_width(request: int, depth: int) -> int:
+    """Effective coalescing factor G: the largest power of two that is
+    <= `request` and divides `depth` (at least 1)."""
+    g = 1
+    while g * 2 <= request and depth % (g * 2) == 0:
+        g *= 2
+    return g
+
+
 class InferencePipeline:
     """Serving-style pipelined inference on one GPU.
 
@@ -143,10 +158,28 @@ class InferencePipeline:
     Every submitted batch runs the full model; nothing is cached or skipped
     — pipelining only overlaps independent batches, as a serving deployment
     would.
+
+    Coalescing: a narrow batch launches narrow grids (the GRU runs
+    batch/16 x 2 workgroups on 256 CUs), so G consecutive submits share one
+    slot of width G*batch. Each submit still copies its input at once (the
+    caller's tensor is free when submit() returns); the submit that fills
+    the slot enqueues the model ONCE at full width plus one D2H. G is
+    `coalesce_width(coalesce, depth)`: `coalesce=None` reads ROKO_COALESCE,
+    else the shipped default; depth 1 or 3 gives G=1, which is exactly the
+    uncoalesced path. There are depth/G slots, so slot memory and the
+    `depth`-submissions validity of copy_out=False predictions are
+    unchanged. Nothing is launched by a timer or a thread: a ticket,
+    drain() and slot reuse flush a partly filled slot first (the model runs
+    at full width over stale rows whose predictions nobody reads, and runs
+    again when the remaining parts arrive), so no caller waits on work that
+    was never enqueued. A caller that only synchronizes the device — as
+    bench.py does after 32 submits per step — sees every batch complete as
+    long as the number of submits is a multiple of G; any power of two
+    <= 32 keeps that true for the benchmark. Votes mode needs G=1.
     """
 
     def __init__(self, model, batch: int, depth: int = 4,
-                 use_graphs: bool = True):
+                 use_graphs: bool = True, coalesce=None):
         from . import require
 
         require()
@@ -156,10 +189,27 @@ class InferencePipeline:
         self.w = _bf16_weights(model)
         self.use_graphs = use_graphs
         dev = next(model.parameters()).device
+        if coalesce is None:
+            coalesce = int(os.environ.get("ROKO_COALESCE", _COALESCE_DEFAULT))
+        # only the C++ slot can be filled in parts
+        cpp_ok = use_graphs and os.environ.get("ROKO_SERVE") != "graph" \
+            and hasattr(_ext(), "ServeSlot")
+        self.coalesce = coalesce_width(coalesce, depth) if cpp_ok else 1
         self.slots = []
-        for _ in range(depth):
-            self.slots.append(_Slot(self, batch, dev))
+        for _ in range(depth // self.coalesce):
+            self.slots.append(_Slot(self, batch, dev, self.coalesce))
         self._next = 0
+
+    def _place(self):
+        """(slot, part) of the next submission k: group (k // G) % (depth //
+        G), part k % G."""
+        k, g = self._next, self.coalesce
+        return self.slots[(k // g) % len(self.slots)], k % g
+
+    def unlaunched(self) -> int:
+        """Submitted batches whose model launch is still deferred."""
+        return sum(s.cpp.unlaunched() for s in self.slots
+                   if s.cpp is not None)
 
     def _forward_amax(self, ids_u8: torch.Tensor) -> torch.Tensor:
         """Static-shape argmax forward (body of roko_argmax, no padding)."""
@@ -184,9 +234,9 @@ class InferencePipeline:
         Returns a ticket; call ticket() to wait and get predictions
         (n, W) uint8 on pinned host memory (a view — copy before the slot
         is reused `depth` submissions later, or pass copy_out=True)."""
-        slot = self.slots[self._next % self.depth]
+        slot, part = self._place()
         self._next += 1
-        return slot.submit(x, copy_out)
+        return slot.submit(x, copy_out, part)
 
     # -- votes mode: predictions stay on the GPU and vote into a device table
     # (ops/votes.py DeviceVotes drives these three) -------------------------
@@ -194,35 +244,54 @@ class InferencePipeline:
         """Pinned staging of the slot the next submit_votes() uses, as numpy
         views x (batch, R, W) u8 and pos (batch, W, 2) i32. The slot is
         synced first: its previous submit read this staging asynchronously."""
+        self._need_uncoalesced()
         return self.slots[self._next % self.depth].votes_staging()
 
     def submit_votes(self, n: int, table: torch.Tensor, n_slots: int,
                      err_flag: torch.Tensor) -> None:
         """Enqueue rows 0..n of the current staging: H2D, model, and one vote
         per column into `table`. No predictions come back."""
+        self._need_uncoalesced()
         slot = self.slots[self._next % self.depth]
         self._next += 1
         slot.submit_votes(n, table, n_slots, err_flag)
 
+    def _need_uncoalesced(self):
+        if self.coalesce != 1:
+            raise RuntimeError(
+                "votes mode needs an uncoalesced pipeline: construct it with "
+                f"coalesce=1 (this one coalesces {self.coalesce} submits)")
+
     def drain(self) -> None:
-        """Wait for every slot; after this all submitted votes are in."""
+        """Launch what is still deferred and wait for every slot; after this
+        all submitted batches and votes are in."""
+        for slot in self.slots:
+            slot.flush()
         for slot in self.slots:
             slot.wait_done()
 
 
 class _Ticket:
     """Handle for one submitted batch; call it to wait and get the (n, W)
-    uint8 predictions. Snapshotted automatically when its slot is reused."""
+    uint8 predictions. Snapshotted automatically when its slot is reused.
+    `need` is the ordinal of the slot launch that covers the submission (0:
+    it was launched by its own submit); the slot is flushed first if that
+    launch has not happened."""
 
-    def __init__(self, slot: "_Slot", n: int):
+    def __init__(self, slot: "_Slot", n: int, part: int = 0, need: int = 0):
         self.slot = slot
         self.n = n
+        self.row0 = part * slot.bp
+        self.need = need
         self.data = None
 
     def materialize(self):
         if self.data is None:
+            if self.slot.launches < self.need:
+                self.slot.flush()
             self.slot.wait_done()
-            self.data = self.slot.host_out[: self.n].clone()
+            self.data = self.slot.host_out[
+                self.row0 : self.row0 + self.n].clone()
 
     def __call__(self) -> torch.Tensor:
         self.materialize()
@@ -243,9 +312,16 @@ class _Slot:
       and replayed per batch; kept for A/B and as the reference backend.
     """
 
-    def __init__(self, pipe: "InferencePipeline", batch: int, dev):
+    def __init__(self, pipe: "InferencePipeline", batch: int, dev,
+                 parts: int = 1):
+        # `parts` consecutive submissions of `batch` rows share this slot
+        # (C++ backend only); the slot is `parts * batch` rows wide
         self.pipe = pipe
-        self.pending = None
+        self.bp = batch
+        self.parts = parts
+        self.pending = [None] * parts
+        self.launches = 0  # model launches of this slot so far
+        batch = batch * parts
         self.host_out = torch.empty(
             (batch, C.WINDOW_COLS), dtype=torch.uint8, pin_memory=True
         )
@@ -254,7 +330,7 @@ class _Slot:
         ext = _ext()
         if pipe.use_graphs and os.environ.get("ROKO_SERVE") != "graph" \
                 and hasattr(ext, "ServeSlot"):
-            self.cpp = ext.ServeSlot(self.pipe.w, batch, self.host_out)
+            self.cpp = ext.ServeSlot(self.pipe.w, batch, self.host_out, parts)
             # one warm-up pass primes the hipBLASLt workspace/algo cache for
             # the slot stream so submit() never allocates
             warm = torch.zeros((batch, C.WINDOW_ROWS, C.WINDOW_COLS),
@@ -287,14 +363,22 @@ class _Slot:
         else:
             self.event.synchronize()
 
+    def unlaunched(self) -> int:
+        return self.cpp.unlaunched() if self.parts > 1 else 0
+
+    def flush(self):
+        """Launch the model for the parts received so far, if any."""
+        if self.parts > 1 and self.cpp.flush():
+            self.launches += 1
+
     def votes_staging(self):
         if self.cpp is None:
             raise RuntimeError(
                 "votes mode needs the C++ serving slot (ext.ServeSlot); it is "
                 "not available with ROKO_SERVE=graph or use_graphs=False")
-        if self.pending is not None:
-            self.pending.materialize()
-            self.pending = None
+        if self.pending[0] is not None:
+            self.pending[0].materialize()
+            self.pending[0] = None
         self.wait_done()
         if getattr(self, "x_stage", None) is None:
             b = self.host_out.shape[0]
@@ -311,15 +395,25 @@ class _Slot:
         self.cpp.submit_votes(self.x_stage, self.pos_stage, n, table,
                               n_slots, err_flag)
 
-    def submit(self, x: torch.Tensor, copy_out: bool):
+    def submit(self, x: torch.Tensor, copy_out: bool, part: int = 0):
         n = x.shape[0]
         # preserve the previous tenant's predictions before the slot buffers
         # are overwritten (its ticket may be called arbitrarily late)
-        if self.pending is not None:
-            self.pending.materialize()
-            self.pending = None
+        if self.pending[part] is not None:
+            self.pending[part].materialize()
+            self.pending[part] = None
         if x.dtype != torch.uint8:
             x = x.to(torch.uint8)
+        if self.parts > 1:
+            # coalesced: the input copy is enqueued now; the model is
+            # enqueued by the submit that fills the slot
+            t = _Ticket(self, n, part, need=self.launches + 1)
+            if self.cpp.submit_part(
+                    x if x.is_contiguous() else x.contiguous(), n, part):
+                self.launches += 1
+            if copy_out:
+                self.pending[part] = t
+            return t
         if self.cpp is not None:
             # ONE C++ call enqueues the whole forward (GIL released). No
             # event sync in the hot path: stream ordering makes buffer
@@ -329,7 +423,7 @@ class _Slot:
             self.cpp.submit(x if x.is_contiguous() else x.contiguous(), n)
             t = _Ticket(self, n)
             if copy_out:
-                self.pending = t
+                self.pending[0] = t
             return t
         self.event.synchronize()  # previous tenant fully drained
         # the input may have been produced on another stream (usually the
@@ -349,7 +443,7 @@ class _Slot:
             self.event.record(self.stream)
         t = _Ticket(self, n)
         if copy_out:
-            self.pending = t
+            self.pending[0] = t
         return t
 
 

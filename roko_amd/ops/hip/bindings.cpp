@@ -664,6 +664,13 @@ struct ServeSlot {
     torch::Tensor host_out;  // (B, 90) u8 pinned
     torch::Tensor seq2d, hseq2d, xg2d;  // cached views for addmm_out
     int B;
+    // coalescing: the slot is filled in `parts` blocks of Bp = B / parts
+    // rows (submit_part) and the model body is launched once per fill.
+    // part_mask: parts received in this round; unlaunched_parts: parts
+    // copied into x_buf that no launch has covered yet.
+    int parts = 1, Bp = 0;
+    uint64_t part_mask = 0;
+    int unlaunched_parts = 0;
     at::cuda::CUDAStream stream;
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
     // front kernel choice (ROKO_FRONT env; v3 default — measured 22.7M vs
@@ -694,6 +701,9 @@ struct ServeSlot {
     // auto default (set in ctor): ON for batch >= 256 where it wins the
     // same-box A/B (b=512: 38.0 vs 36.4 M bases/s), OFF at b=128 where the
     // graph launch costs more than the direct enqueues (26.6 vs 27.7).
+    // Re-measured with 4 hardware queues at the coalesced widths: the
+    // graph wins at 256 / 512 / 1024 (29.5 / 33.3 / 35.3 vs 27.0 / 31.9 /
+    // 34.8) and loses at 128 (19.9 vs 20.0) — the rule stands.
     bool use_gslot = false;
     bool xg2_path = false;   // set in ctor: raw (capture-legal) layer path
     hipGraph_t slot_graph = nullptr;
@@ -708,9 +718,13 @@ struct ServeSlot {
     hipGraphExec_t votes_gexec = nullptr;
     bool votes_capture_failed = false;
 
-    ServeSlot(py::dict w, int B_, torch::Tensor host_out_)
-        : B(B_), stream(at::cuda::getStreamFromPool(/*high_priority=*/false)) {
+    ServeSlot(py::dict w, int B_, torch::Tensor host_out_, int parts_ = 1)
+        : B(B_), parts(parts_),
+          stream(at::cuda::getStreamFromPool(/*high_priority=*/false)) {
         namespace t = torch;
+        TORCH_CHECK(parts >= 1 && parts <= 64 && B % parts == 0,
+                    "parts must be in 1..64 and divide the slot batch");
+        Bp = B / parts;
         auto need = [&](const char* k) {
             torch::Tensor v = w[k].cast<torch::Tensor>();
             TORCH_CHECK(v.is_cuda() && v.is_contiguous(), "weight ", k);
@@ -871,14 +885,17 @@ struct ServeSlot {
                      nullptr, amax.data_ptr<uint8_t>(), 90, B, s);
     }
 
-    void run(torch::Tensor x, int64_t n) {
+    // input half of a submit: order the slot stream behind the producer of
+    // x and copy rows [0, n) of x into x_buf rows [row0, row0 + n). The read
+    // of x is enqueued here, never deferred.
+    void copy_in(const torch::Tensor& x, int64_t n, int64_t row0) {
         // x may live on the GPU or on (ideally pinned) host memory — the
         // copy into the static slot buffer below is D2D or H2D accordingly
         TORCH_CHECK(x.scalar_type() == torch::kUInt8 && x.is_contiguous() &&
-                        n <= B,
+                        n >= 0 && row0 >= 0 && row0 + n <= B &&
+                        x.numel() >= n * 200 * 90,
                     "x must be contiguous u8, n <= slot batch");
-        // order the slot stream behind the producer of x, then enqueue the
-        // whole forward on the slot stream
+        // order the slot stream behind the producer of x
         auto prod = at::cuda::getCurrentCUDAStream();
         (void)hipEventRecord(ev_in, prod.stream());
         (void)hipStreamWaitEvent(stream.stream(), ev_in, 0);
@@ -889,14 +906,25 @@ struct ServeSlot {
         if (x.is_cuda())
             c10::cuda::CUDACachingAllocator::recordStream(
                 x.storage().data_ptr(), stream);
+        if (n == 0) return;
         if (use_fold || xg2_path) {
-            // torch-free path: raw copies + kernels, optionally one
-            // hipGraphLaunch replacing the per-batch kernel enqueues
+            (void)hipMemcpyAsync(
+                x_buf.data_ptr<uint8_t>() + (size_t)row0 * 200 * 90,
+                x.data_ptr(), (size_t)n * 200 * 90, hipMemcpyDefault,
+                stream.stream());
+        } else {
+            at::cuda::CUDAStreamGuard guard(stream);
+            x_buf.narrow(0, row0, n).copy_(x.narrow(0, 0, n), true);
+        }
+    }
+
+    // model half of a submit: the whole forward at full slot width on the
+    // slot stream, one D2H of amax into the pinned host_out, ev_done
+    void launch_body() {
+        if (use_fold || xg2_path) {
+            // torch-free path: raw kernels, optionally one hipGraphLaunch
+            // replacing the per-batch kernel enqueues
             hipStream_t s = stream.stream();
-            if (n > 0)
-                (void)hipMemcpyAsync(x_buf.data_ptr(), x.data_ptr(),
-                                     (size_t)n * 200 * 90, hipMemcpyDefault,
-                                     s);
             // the first run executes eagerly (warms caches); the second
             // captures + launches; later runs just launch
             if (use_gslot && !slot_gexec && n_runs >= 1) try_capture(s);
@@ -911,13 +939,51 @@ struct ServeSlot {
             ++n_runs;
         } else {
             at::cuda::CUDAStreamGuard guard(stream);
-            hipStream_t s = stream.stream();
-            if (n > 0) x_buf.narrow(0, 0, n).copy_(x.narrow(0, 0, n), true);
-            enqueue_model_lt(s);
+            enqueue_model_lt(stream.stream());
             host_out.copy_(amax, true);
         }
+        unlaunched_parts = 0;
         (void)hipEventRecord(ev_done, stream.stream());
     }
+
+    void run(torch::Tensor x, int64_t n) {
+        copy_in(x, n, 0);
+        part_mask = 0;
+        launch_body();
+    }
+
+    // Coalesced submit: rows [0, n) of x become rows [part*Bp, part*Bp + n)
+    // of the slot. The input copy is enqueued now (x may be freed or
+    // overwritten as soon as this returns); the model body is enqueued once,
+    // at full width, by the call that completes the round (every part seen).
+    // Returns true when this call launched the body.
+    bool submit_part(torch::Tensor x, int64_t n, int64_t part) {
+        TORCH_CHECK(part >= 0 && part < parts && n <= Bp,
+                    "part out of range or n > part rows");
+        copy_in(x, n, part * Bp);
+        part_mask |= uint64_t(1) << part;
+        ++unlaunched_parts;
+        const uint64_t full =
+            parts == 64 ? ~uint64_t(0) : (uint64_t(1) << parts) - 1;
+        if (part_mask != full) return false;
+        part_mask = 0;
+        launch_body();
+        return true;
+    }
+
+    // Launch the body for a partly filled slot (rows of parts not yet
+    // received hold stale input, like rows n..B of a short batch; their
+    // predictions are ignored). The round is not reset: the parts still to
+    // come land in their usual rows and the call that completes the round
+    // launches the body again. Returns true if anything was launched.
+    bool flush() {
+        if (unlaunched_parts == 0) return false;
+        launch_body();
+        return true;
+    }
+
+    // parts copied into the slot that no launch has covered yet
+    int64_t unlaunched() const { return unlaunched_parts; }
 
     void sync() {
         hipError_t e = hipEventSynchronize(ev_done);
@@ -949,6 +1015,7 @@ struct ServeSlot {
     void submit_votes(torch::Tensor x, torch::Tensor pos, int64_t n,
                       torch::Tensor table, int64_t n_slots,
                       torch::Tensor err_flag) {
+        TORCH_CHECK(parts == 1, "votes mode needs an uncoalesced slot");
         TORCH_CHECK(x.scalar_type() == torch::kUInt8 && x.is_contiguous() &&
                         n >= 0 && n <= B && x.numel() >= n * 200 * 90,
                     "x must be contiguous u8 with n <= slot batch rows");
@@ -1081,11 +1148,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("vote_consensus", &vote_consensus, py::arg("table"),
           py::arg("n_slots"), py::arg("maj"));
     py::class_<ServeSlot>(m, "ServeSlot")
-        .def(py::init<py::dict, int, torch::Tensor>(), py::arg("weights"),
-             py::arg("batch"), py::arg("host_out"))
+        .def(py::init<py::dict, int, torch::Tensor, int>(),
+             py::arg("weights"), py::arg("batch"), py::arg("host_out"),
+             py::arg("parts") = 1)
         .def("run", &ServeSlot::run, py::arg("x"), py::arg("n"))
         .def("submit", &ServeSlot::submit, py::arg("x"), py::arg("n"),
              py::call_guard<py::gil_scoped_release>())
+        .def("submit_part", &ServeSlot::submit_part, py::arg("x"),
+             py::arg("n"), py::arg("part"),
+             py::call_guard<py::gil_scoped_release>())
+        .def("flush", &ServeSlot::flush,
+             py::call_guard<py::gil_scoped_release>())
+        .def("unlaunched", &ServeSlot::unlaunched)
+        .def_readonly("parts", &ServeSlot::parts)
         .def("sync", &ServeSlot::sync,
              py::call_guard<py::gil_scoped_release>())
         .def("done", &ServeSlot::done)

@@ -39,8 +39,9 @@ class DeviceVotes:
 
     `contig_lens` maps contig name -> draft length. Tables are allocated
     zeroed on a contig's first batch and released by `free()`. With a
-    `pipe` (ops.forward.InferencePipeline) batches go through its serving
-    slots in votes mode: fill `staging()`, then `add_batch(contig, n)`.
+    `pipe` (ops.forward.InferencePipeline built with coalesce=1) batches go
+    through its serving slots in votes mode: fill `staging()`, then
+    `add_batch(contig, n)`.
     `scatter()` adds given predictions directly (tests, merging).
     """
 

@@ -48,8 +48,10 @@ class _DeviceSink:
         from .ops.votes import DeviceVotes
 
         self.batch = batch
+        # votes mode runs one batch per slot (coalesce=1)
         self.dv = DeviceVotes(lens, InferencePipeline(model, batch,
-                                                      depth=depth))
+                                                      depth=depth,
+                                                      coalesce=1))
         self.x = self.pos = None
         self.fill = 0
 
