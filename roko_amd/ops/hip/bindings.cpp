@@ -23,7 +23,7 @@ void embed_mlp_fwd2(const uint8_t* ids, const void* w1g, const float* b1,
 void embed_mlp_fwd3(const uint8_t* ids, const void* w1g, const float* b1,
                     const void* w2, const float* b2, const void* emb,
                     void* out, int B, hipStream_t stream,
-                    unsigned long long* timing);
+                    unsigned long long* timing, int ldo = 500);
 void gru_layer_fwd(const void* xg, const void* u, const float* bhh, void* hseq,
                    void* cache, int T, int B, hipStream_t stream, uint32_t dbg);
 void gru_layer_fwd_fused(const void* x, const void* w_ih_p, const void* b_ih,
@@ -64,6 +64,9 @@ void xg_gemm(const void* A, const void* B, const void* bias, void* C, int M,
 void xg_gemm2(const void* A, const void* Bt, const void* bias, void* C,
               int M, int KREAL, int KP, hipStream_t stream,
               unsigned long long* timing = nullptr);
+void xg_gemm3(const void* A, int lda, const void* Bt, const void* bias,
+              void* C, int M, int KP, hipStream_t stream);
+int xg_gemm3_tile_m();
 int atb_splitk_nslices(int K);
 void atb_splitk(const void* A, const void* B, float* ws, float* C, int M,
                 int N, int K, hipStream_t stream);
@@ -158,7 +161,9 @@ torch::Tensor embed_mlp_fwd2(torch::Tensor ids, torch::Tensor w1g,
 torch::Tensor embed_mlp_fwd3(torch::Tensor ids, torch::Tensor w1g,
                              torch::Tensor b1, torch::Tensor w2,
                              torch::Tensor b2, torch::Tensor emb,
-                             c10::optional<torch::Tensor> timing = c10::nullopt) {
+                             c10::optional<torch::Tensor> timing = c10::nullopt,
+                             int64_t ldo = 500,
+                             c10::optional<torch::Tensor> out_ = c10::nullopt) {
     check(ids, torch::kUInt8, "ids");
     check(w1g, torch::kBFloat16, "w1g");
     check(b1, torch::kFloat32, "b1");
@@ -169,14 +174,29 @@ torch::Tensor embed_mlp_fwd3(torch::Tensor ids, torch::Tensor w1g,
     TORCH_CHECK(ids.size(1) == 200 && ids.size(2) == 90, "ids must be (B,200,90)");
     TORCH_CHECK(w1g.size(0) == 112 && w1g.size(1) == 232,
                 "w1g must be (112,232) zero-padded");
-    auto out = torch::empty({90, B, 500}, ids.options().dtype(torch::kBFloat16));
+    // ldo: output row stride. Columns [500, ldo) are never written, so a
+    // padded output is returned zero-filled (or is the caller's `out`)
+    TORCH_CHECK(ldo == 500 || (ldo > 500 && ldo % 8 == 0),
+                "ldo must be 500 or a multiple of 8 above it");
+    torch::Tensor out;
+    if (out_.has_value()) {
+        out = *out_;
+        check(out, torch::kBFloat16, "out");
+        TORCH_CHECK(out.dim() == 3 && out.size(0) == 90 && out.size(1) == B &&
+                        out.size(2) == ldo, "out must be (90, B, ldo)");
+    } else if (ldo == 500) {
+        out = torch::empty({90, B, 500}, ids.options().dtype(torch::kBFloat16));
+    } else {
+        out = torch::zeros({90, B, ldo}, ids.options().dtype(torch::kBFloat16));
+    }
     rk::embed_mlp_fwd3(ids.data_ptr<uint8_t>(), w1g.data_ptr(),
                        b1.data_ptr<float>(), w2.data_ptr(),
                        b2.data_ptr<float>(), emb.data_ptr(), out.data_ptr(),
                        B, cur_stream(),
                        timing ? reinterpret_cast<unsigned long long*>(
                                     timing->data_ptr<int64_t>())
-                              : nullptr);
+                              : nullptr,
+                       (int)ldo);
     return out;
 }
 
@@ -425,6 +445,40 @@ torch::Tensor xg_gemm2(torch::Tensor A, torch::Tensor Bt, torch::Tensor bias,
     return C;
 }
 
+// xg projection at the coalesced serving width (docs/KERNELS.md lesson 21):
+// A (M, 256|512) bf16, rows 16-B aligned with any leading dimension (a
+// column slice of a wider buffer is fine) x Bt (768, KP) + bias -> (M, 768).
+// Byte-identical to xg_gemm2 on the same values.
+torch::Tensor xg_gemm3(torch::Tensor A, torch::Tensor Bt, torch::Tensor bias,
+                       c10::optional<torch::Tensor> out_) {
+    check(Bt, torch::kBFloat16, "Bt");
+    check(bias, torch::kBFloat16, "bias");
+    TORCH_CHECK(A.is_cuda() && A.scalar_type() == torch::kBFloat16 &&
+                    A.dim() == 2, "A must be a 2-D bf16 GPU tensor");
+    const int64_t M = A.size(0), KP = A.size(1);
+    TORCH_CHECK(KP == 256 || KP == 512, "A must be (M, 256|512)");
+    const int64_t lda = M > 1 ? A.stride(0) : KP;
+    TORCH_CHECK(A.stride(1) == 1 && lda >= KP && lda % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0,
+                "A rows must be unit-stride and 16-byte aligned");
+    TORCH_CHECK(Bt.size(0) == 768 && Bt.size(1) == KP, "Bt must be (768, KP)");
+    TORCH_CHECK(bias.numel() == 768, "bias must be (768)");
+    TORCH_CHECK(M > 0 && M % rk::xg_gemm3_tile_m() == 0,
+                "M must be a positive multiple of ", rk::xg_gemm3_tile_m());
+    torch::Tensor C;
+    if (out_.has_value()) {
+        C = *out_;
+        check(C, torch::kBFloat16, "out");
+        TORCH_CHECK(C.dim() == 2 && C.size(0) == M && C.size(1) == 768,
+                    "out must be (M, 768)");
+    } else {
+        C = torch::empty({M, 768}, A.options());
+    }
+    rk::xg_gemm3(A.data_ptr(), (int)lda, Bt.data_ptr(), bias.data_ptr(),
+                 C.data_ptr(), (int)M, (int)KP, cur_stream());
+    return C;
+}
+
 // GRU layer weight gradients in ONE binding call: dU (both dirs, via
 // strided-slice split-K AtB — the t-shifted h_prev pairing makes both
 // operands regular slices, no torch.cat), dW_ih, and the three bias
@@ -657,7 +711,9 @@ struct ServeSlot {
     torch::Tensor hseq2;                // ping-pong buffer for the fold path
     // slot state + workspaces
     torch::Tensor x_buf;     // (B, 200, 90) u8 static input
-    torch::Tensor seq;       // (90, B, 500) bf16 front output
+    torch::Tensor seq;       // (90, B, seq_ld) bf16 front output; seq_ld is
+                             // 500, or 512 on the xg3 path (cols 500..511
+                             // zeroed once here and never written again)
     torch::Tensor xg;        // (90*B, 768) bf16 per-layer gate inputs
     torch::Tensor hseq;      // (90, B, 2, 128) bf16 per-layer output
     torch::Tensor amax;      // (B, 90) u8 fused-argmax predictions
@@ -704,8 +760,16 @@ struct ServeSlot {
     // Re-measured with 4 hardware queues at the coalesced widths: the
     // graph wins at 256 / 512 / 1024 (29.5 / 33.3 / 35.3 vs 27.0 / 31.9 /
     // 34.8) and loses at 128 (19.9 vs 20.0) — the rule stands.
+    // xg_gemm3 for the three projections (ROKO_XG3=0 keeps xg_gemm2 and the
+    // 500-stride front output — the A/B partner and bit-exact reference)
+    bool use_xg3 = [] {
+        const char* f = getenv("ROKO_XG3");
+        return !(f && std::string(f) == "0");
+    }();
     bool use_gslot = false;
     bool xg2_path = false;   // set in ctor: raw (capture-legal) layer path
+    bool xg3_path = false;   // set in ctor: xg2_path taken with xg_gemm3
+    int seq_ld = 500;
     hipGraph_t slot_graph = nullptr;
     hipGraphExec_t slot_gexec = nullptr;
     int n_runs = 0;
@@ -748,6 +812,13 @@ struct ServeSlot {
             use_xg2 = false;
         }
         xg2_path = use_xg2 && !w_ih_p.empty() && ((90 * B_) % 256) == 0;
+        // xg3 needs the front that takes a leading dimension (v3) and the
+        // K-padded layer-0 weight image its A rows are padded to match
+        xg3_path = xg2_path && use_xg3 && !use_fold && use_v3 &&
+                   w1gt.defined() && ((90 * B_) % rk::xg_gemm3_tile_m()) == 0 &&
+                   w_ih_p[0].size(1) == 512 && w_ih_p[1].size(1) == 256 &&
+                   w_ih_p[2].size(1) == 256;
+        seq_ld = xg3_path ? 512 : 500;
         if (const char* f = getenv("ROKO_GSLOT"))
             use_gslot = std::string(f) == "1";
         else
@@ -759,12 +830,15 @@ struct ServeSlot {
         host_out = host_out_;
         auto dev = w1.options();
         x_buf = t::zeros({B, 200, 90}, dev.dtype(t::kUInt8));
-        seq = t::empty({90, B, 500}, dev.dtype(t::kBFloat16));
+        // zeros, not empty: on the xg3 path the GEMM multiplies the pad
+        // columns by W's zero padding, and 0 x NaN from stale memory is NaN
+        seq = xg3_path ? t::zeros({90, B, 512}, dev.dtype(t::kBFloat16))
+                       : t::empty({90, B, 500}, dev.dtype(t::kBFloat16));
         xg = t::empty({(int64_t)90 * B, 768}, dev.dtype(t::kBFloat16));
         hseq = t::empty({90, B, 2, 128}, dev.dtype(t::kBFloat16));
         if (use_fold) hseq2 = t::empty({90, B, 2, 128}, dev.dtype(t::kBFloat16));
         amax = t::empty({B, 90}, dev.dtype(t::kUInt8));
-        seq2d = seq.view({(int64_t)90 * B, 500});
+        seq2d = seq.view({(int64_t)90 * B, seq_ld});  // lt path: seq_ld 500
         hseq2d = hseq.view({(int64_t)90 * B, 256});
         xg2d = xg;
         (void)hipEventCreateWithFlags(&ev_in, hipEventDisableTiming);
@@ -787,7 +861,7 @@ struct ServeSlot {
             rk::embed_mlp_fwd3(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
                                b1.data_ptr<float>(), w2.data_ptr(),
                                b2.data_ptr<float>(), emb.data_ptr(),
-                               seq.data_ptr(), B, s, nullptr);
+                               seq.data_ptr(), B, s, nullptr, seq_ld);
         else if (w1gt.defined())
             rk::embed_mlp_fwd2(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
                                b1.data_ptr<float>(), w2.data_ptr(),
@@ -813,10 +887,16 @@ struct ServeSlot {
             }
         } else {
             for (int l = 0; l < 3; ++l) {
-                rk::xg_gemm2((l == 0 ? seq : hseq).data_ptr(),
-                             w_ih_p[l].data_ptr(), b_ih[l].data_ptr(),
-                             xg.data_ptr(), 90 * B, l == 0 ? 500 : 256,
-                             (int)w_ih_p[l].size(1), s);
+                if (xg3_path)
+                    rk::xg_gemm3((l == 0 ? seq : hseq).data_ptr(),
+                                 l == 0 ? 512 : 256, w_ih_p[l].data_ptr(),
+                                 b_ih[l].data_ptr(), xg.data_ptr(), 90 * B,
+                                 l == 0 ? 512 : 256, s);
+                else
+                    rk::xg_gemm2((l == 0 ? seq : hseq).data_ptr(),
+                                 w_ih_p[l].data_ptr(), b_ih[l].data_ptr(),
+                                 xg.data_ptr(), 90 * B, l == 0 ? 500 : 256,
+                                 (int)w_ih_p[l].size(1), s);
                 rk::gru_layer_fwd(xg.data_ptr(), u[l].data_ptr(),
                                   bhh[l].data_ptr<float>(), hseq.data_ptr(),
                                   nullptr, 90, B, s, 0);
@@ -1100,7 +1180,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("embed_mlp_fwd2", &embed_mlp_fwd2);
     m.def("embed_mlp_fwd3", &embed_mlp_fwd3, py::arg("ids"), py::arg("w1g"),
           py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("emb"),
-          py::arg("timing") = c10::nullopt);
+          py::arg("timing") = c10::nullopt, py::arg("ldo") = 500,
+          py::arg("out") = c10::nullopt);
     m.def("embed_mlp_fwd", &embed_mlp_fwd, py::arg("ids"), py::arg("w1"),
           py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("emb"),
           py::arg("dbg") = 0, py::arg("timing") = c10::nullopt);
@@ -1133,6 +1214,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("head_wgrads", &head_wgrads);
     m.def("xg_gemm2", &xg_gemm2, py::arg("A"), py::arg("Bt"), py::arg("bias"),
           py::arg("timing") = py::none());
+    m.def("xg_gemm3", &xg_gemm3, py::arg("A"), py::arg("Bt"), py::arg("bias"),
+          py::arg("out") = py::none());
     m.def("front_de_timed", &front_de_timed, py::arg("ids"), py::arg("dt1g"),
           py::arg("w1"), py::arg("seed"), py::arg("keep"), py::arg("dbg") = 0);
     m.def("front_bwd", &front_bwd, py::arg("ids"), py::arg("dseq"),

@@ -472,8 +472,9 @@ __global__ __launch_bounds__(WAVES3 * 64, 1) void embed_mlp_fwd3_kernel(
     const bf16* __restrict__ w2,      // (F2, F1)
     const float* __restrict__ b2,     // (F2)
     const bf16* __restrict__ emb,     // (12, E)
-    bf16* __restrict__ out,           // (W, B, OUT)
+    bf16* __restrict__ out,           // (W, B, ldo): cols [0, OUT) written
     int B,
+    int ldo,                          // output row stride (elements, % 8 == 0)
     unsigned long long* __restrict__ timing) {  // optional (6): per-phase
                                                 // cycle sums from lane 0
     __shared__ struct {
@@ -682,7 +683,7 @@ __global__ __launch_bounds__(WAVES3 * 64, 1) void embed_mlp_fwd3_kernel(
         V3_T1(3);
         // ---- coalesced store (wave-wide b128) -----------------------------
         {
-            bf16* dst = out + ((size_t)w * B + b) * OUT;
+            bf16* dst = out + ((size_t)w * B + b) * ldo;
             const int e8 = lane * 8;
             if (e8 + 8 <= OUT)
                 *reinterpret_cast<bf16x8*>(dst + e8) =
@@ -704,13 +705,13 @@ __global__ __launch_bounds__(WAVES3 * 64, 1) void embed_mlp_fwd3_kernel(
 void embed_mlp_fwd3(const uint8_t* ids, const void* w1g, const float* b1,
                     const void* w2, const float* b2, const void* emb,
                     void* out, int B, hipStream_t stream,
-                    unsigned long long* timing) {
+                    unsigned long long* timing, int ldo) {
     hipLaunchKernelGGL(v3::embed_mlp_fwd3_kernel, dim3(B),
                        dim3(v3::WAVES3 * 64), 0, stream, ids,
                        static_cast<const bf16*>(w1g), b1,
                        static_cast<const bf16*>(w2), b2,
                        static_cast<const bf16*>(emb), static_cast<bf16*>(out),
-                       B, timing);
+                       B, ldo, timing);
 }
 
 void embed_mlp_fwd2(const uint8_t* ids, const void* w1g, const float* b1,

@@ -610,6 +610,209 @@ void xg_gemm2(const void* A, const void* Bt, const void* bias, void* C,
                            static_cast<bf16*>(C), M, timing);
 }
 
+// ---------------------------------------------------------------------------
+// xg_gemm3: xg_gemm2 re-shaped for the coalesced serving width (M = 92160,
+// 4320 tiles instead of 270 — docs/KERNELS.md lesson 21). Same arithmetic
+// (one 16x16x32 accumulator chain per output, k ascending, fp32 bias add,
+// one bf16 round), so the output equals xg_gemm2's byte for byte. What
+// changed around the MFMAs:
+//   * 128x128 tile, 4 waves of 64x64 (8 fragment reads per 16 MFMAs, not
+//     10), 64 KB of LDS -> TWO workgroups per CU: one block's barrier skew
+//     and epilogue run under the other block's MFMA bursts;
+//   * 1-D grid with the bijective XCD remap: the six n-tiles of one m-tile
+//     run back to back on one XCD, so an A tile leaves HBM once and the
+//     other five reads hit that XCD's L2;
+//   * A rows are 16-B aligned with a leading dimension (the layer-0 input
+//     is a 512-stride zero-padded buffer): every staging access is b128 and
+//     one 8-lane group reads one full 128-B line. No K=500 select;
+//   * unpadded 128-B LDS rows with the 16-B chunk index XORed by
+//     (row >> 1) & 7: conflict-free for ds_read_b128's four 16-lane groups
+//     (the 144-B pitch of xg_gemm2 is 2-way conflicted on 7 of 8 rows) and
+//     for the b128 staging writes;
+//   * the MFMA takes the W fragment as its A operand, so a lane holds four
+//     CONSECUTIVE output columns of one row; the tile goes through a
+//     wave-private swizzled LDS image (the dead staging buffers) and leaves
+//     as b128 stores, eight lanes covering one 128-B line per row.
+namespace xg3 {
+
+constexpr int XN = 768;
+constexpr int BM = 128;   // C rows per workgroup
+constexpr int BN = 128;   // C cols per workgroup
+constexpr int BK = 64;    // k-slice per stage (128-B LDS rows)
+constexpr int WAVES = 4;  // 2 (m) x 2 (n), 64x64 per wave
+constexpr int NT = XN / BN;
+constexpr int TILE_BYTES = BM * BK * 2;  // one operand, one buffer: 16 KB
+
+// byte offset of 16-B chunk q (0..7) of row `row` in a [rows][64] image
+RK_DEV int swz(int row, int q) {
+    return row * 128 + ((q ^ ((row >> 1) & 7)) << 4);
+}
+
+template <int KP>
+__global__ __launch_bounds__(WAVES * 64, 2) void xg_gemm3_kernel(
+    const bf16* __restrict__ A,     // (M, KP) rows strided by lda (16-B rows)
+    const bf16* __restrict__ Bt,    // (768, KP) row-major = B^T, zero-padded
+    const bf16* __restrict__ bias,  // (768)
+    bf16* __restrict__ C,           // (M, 768)
+    int lda, int nwg) {
+    constexpr int KB = KP / BK;
+    // [buf][A | B][16 KB]; the epilogue reuses it as 4 x 8 KB wave images
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * 2 * TILE_BYTES];
+
+    const int tid = threadIdx.x;
+    const int wid = tid >> 6;
+    const int lane = tid & 63;
+    const int lrow = lane >> 4;
+    const int lcol = lane & 15;
+    const int wm = wid >> 1, wn = wid & 1;
+
+    // bijective XCD remap: workgroups that share blockIdx % 8 share an XCD
+    // and are dispatched in blockIdx order, so give each such group one
+    // contiguous run of tile ids (n fastest)
+    const int orig = blockIdx.x;
+    const int xcd = orig & 7;
+    const int q8 = nwg >> 3, r8 = nwg & 7;
+    const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8)
+                     + (orig >> 3);
+    const int m0 = (wgid / NT) * BM;
+    const int n0 = (wgid % NT) * BN;
+
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // staging: each operand slice is 128 rows x 128 B = 4 b128 per thread,
+    // 8 threads per row. Two register sets, committed after the MFMA burst
+    // that follows their issue (the xg_gemm2 schedule).
+    bf16x8 ra[2][4], rb[2][4];
+    const int s_row = tid >> 3, s_q = tid & 7;
+    const bf16* a_src = A + (size_t)(m0 + s_row) * lda + s_q * 8;
+    const bf16* b_src = Bt + (size_t)(n0 + s_row) * KP + s_q * 8;
+    const int s_off = swz(s_row, s_q);  // + p * 32 rows: swizzle unchanged
+    auto issue = [&](int kq, bf16x8(&va)[4], bf16x8(&vb)[4]) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            va[p] = *reinterpret_cast<const bf16x8*>(
+                a_src + (size_t)p * 32 * lda + kq * BK);
+            vb[p] = *reinterpret_cast<const bf16x8*>(
+                b_src + (size_t)p * 32 * KP + kq * BK);
+        }
+    };
+    auto commit = [&](int buf, bf16x8(&va)[4], bf16x8(&vb)[4]) {
+        unsigned char* ab = lds + buf * 2 * TILE_BYTES;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            *reinterpret_cast<bf16x8*>(ab + p * 32 * 128 + s_off) = va[p];
+            *reinterpret_cast<bf16x8*>(ab + TILE_BYTES + p * 32 * 128 + s_off) =
+                vb[p];
+        }
+    };
+    // fragment reads: row = 16-row subtile + lcol, chunk = kh * 4 + lrow
+    const int fsw = (lcol >> 1) & 7;
+    const int fa_off = (wm * 64 + lcol) * 128;
+    const int fb_off = TILE_BYTES + (wn * 64 + lcol) * 128;
+    auto mfma_step = [&](int buf) {
+        const unsigned char* ab = lds + buf * 2 * TILE_BYTES;
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh) {
+            const int ch = ((kh * 4 + lrow) ^ fsw) << 4;
+            bf16x8 af[4], wf[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                af[t] = *reinterpret_cast<const bf16x8*>(
+                    ab + fa_off + t * 16 * 128 + ch);
+                wf[t] = *reinterpret_cast<const bf16x8*>(
+                    ab + fb_off + t * 16 * 128 + ch);
+            }
+            // W fragment as the A operand: D[n][m], lane (lrow, lcol) holds
+            // C[m = lcol][n = lrow * 4 + i]
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt)
+                    acc[mt][nt] = mfma16x16x32(wf[nt], af[mt], acc[mt][nt]);
+        }
+    };
+
+    // slice kq + 2 is issued into the set slice kq was committed from, BEFORE
+    // slice kq's MFMA burst: its loads stay in flight across two bursts and
+    // the barrier between them (the commit waits a counted vmcnt(8))
+    issue(0, ra[0], rb[0]);
+    if (KB > 1) issue(1, ra[1], rb[1]);
+    commit(0, ra[0], rb[0]);
+    __syncthreads();
+#pragma unroll
+    for (int kq = 0; kq < KB; ++kq) {
+        if (kq + 2 < KB) issue(kq + 2, ra[kq & 1], rb[kq & 1]);
+        mfma_step(kq & 1);
+        if (kq + 1 < KB) commit((kq + 1) & 1, ra[(kq + 1) & 1],
+                                rb[(kq + 1) & 1]);
+        __syncthreads();
+    }
+
+    // epilogue: fp32 bias add, one bf16 round, 8-B packed writes into this
+    // wave's 64 x 128-B image (chunk ^ (row & 7)), then b128 row reads and
+    // b128 global stores — 8 lanes per 128-B line of C
+    unsigned char* img = lds + wid * (64 * 128);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int nl = nt * 16 + lrow * 4;
+        bf16x4 bv = *reinterpret_cast<const bf16x4*>(
+            reinterpret_cast<const __bf16*>(bias) + n0 + wn * 64 + nl);
+        float br[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) br[i] = (float)bv[i];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const int row = mt * 16 + lcol;
+            alignas(8) bf16 o[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = f2bf(acc[mt][nt][i] + br[i]);
+            *reinterpret_cast<uint64_t*>(
+                img + row * 128 + (((nl >> 3) ^ (row & 7)) << 4) +
+                (nl & 4) * 2) = *reinterpret_cast<const uint64_t*>(o);
+        }
+    }
+    __syncthreads();
+    {
+        const int r8l = lane >> 3, j = lane & 7;
+        bf16* cdst = C + (size_t)(m0 + wm * 64 + r8l) * XN + n0 + wn * 64 + j * 8;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const int row = p * 8 + r8l;
+            *reinterpret_cast<bf16x8*>(cdst + (size_t)p * 8 * XN) =
+                *reinterpret_cast<const bf16x8*>(
+                    img + row * 128 + ((j ^ (row & 7)) << 4));
+        }
+    }
+}
+
+}  // namespace xg3
+
+// A (M, KP) with leading dimension lda (elements, % 8 == 0, 16-B aligned
+// base), M % 128 == 0, KP in {256, 512}
+void xg_gemm3(const void* A, int lda, const void* Bt, const void* bias,
+              void* C, int M, int KP, hipStream_t stream) {
+    const int nwg = (M / xg3::BM) * xg3::NT;
+    dim3 grid(nwg), block(xg3::WAVES * 64);
+    if (KP == 512)
+        hipLaunchKernelGGL((xg3::xg_gemm3_kernel<512>), grid, block, 0, stream,
+                           static_cast<const bf16*>(A),
+                           static_cast<const bf16*>(Bt),
+                           static_cast<const bf16*>(bias),
+                           static_cast<bf16*>(C), lda, nwg);
+    else if (KP == 256)
+        hipLaunchKernelGGL((xg3::xg_gemm3_kernel<256>), grid, block, 0, stream,
+                           static_cast<const bf16*>(A),
+                           static_cast<const bf16*>(Bt),
+                           static_cast<const bf16*>(bias),
+                           static_cast<bf16*>(C), lda, nwg);
+}
+
+int xg_gemm3_tile_m() { return xg3::BM; }
+
 void xg_gemm(const void* A, const void* B, const void* bias, void* C, int M,
              int KP, hipStream_t stream) {
     dim3 grid(M / (xggemm::WAVES * xggemm::WM), xggemm::XN / xggemm::BN);
