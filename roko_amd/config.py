@@ -109,6 +109,10 @@ class FeatureConfig:
     #: worker scheduling (the reference re-seeds srand(time) per call instead,
     #: gen.cpp:12 — deliberately fixed here).
     seed: int = 0
+    #: row sampler: "mt19937" (one sequential stream per region, the default)
+    #: or "counter" (stateless hash of (region, window, row) — the rule the
+    #: GPU window builder implements, ops/cpp/pileup.h)
+    sampler: str = "mt19937"
 
 
 @dataclass

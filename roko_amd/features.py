@@ -7,7 +7,7 @@ truth labels before writing.
 
 Usage:
   python -m roko_amd.features <draft.fasta> <reads.bam> <out.rkw>
-      [--Y truth.bam] [--t workers] [--seed N]
+      [--Y truth.bam] [--t workers] [--seed N] [--sampler mt19937|counter]
 """
 
 from __future__ import annotations
@@ -54,7 +54,35 @@ def _features_for_region(bam, contig, start, end, cfg: FeatureConfig):
         filter_flag=cfg.filter_flag,
         min_mapq=cfg.min_mapq,
         seed=cfg.seed,
+        sampler=cfg.sampler,
     )
+
+
+def _reads_for_region(bam, contig, start, end, cfg: FeatureConfig):
+    from .ops import _pileup
+
+    return _pileup.region_reads(
+        bam,
+        contig,
+        start,
+        end,
+        filter_flag=cfg.filter_flag,
+        min_mapq=cfg.min_mapq,
+        seed=cfg.seed,
+    )
+
+
+def generate_reads(args):
+    """Worker of the device extraction route: the region's filtered reads,
+    still packed as BAM stores them (ops/windows.py builds the windows from
+    them on the GPU). Failures are returned, not raised, as in
+    generate_infer."""
+    bam_x, contig, start, end, cfg = args
+    try:
+        pack = _reads_for_region(bam_x, contig, start, end, cfg)
+    except Exception as e:  # noqa: BLE001 — deliberate region-level fence
+        return ("__error__", f"{contig}:{start}-{end}", repr(e))
+    return contig, start, end, pack
 
 
 def generate_infer(args):
@@ -222,8 +250,10 @@ def main(argv=None):
     p.add_argument("--Y", default=None, help="truth-to-draft BAM (training mode)")
     p.add_argument("--t", type=int, default=1, help="worker processes")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--sampler", choices=("mt19937", "counter"),
+                   default="mt19937", help="row sampler (ops/cpp/pileup.h)")
     a = p.parse_args(argv)
-    cfg = FeatureConfig(seed=a.seed)
+    cfg = FeatureConfig(seed=a.seed, sampler=a.sampler)
     run(a.ref, a.X, a.o, bam_y=a.Y, workers=a.t, cfg=cfg)
 
 

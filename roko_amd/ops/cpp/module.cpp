@@ -18,8 +18,14 @@ namespace py = pybind11;
 static py::tuple generate_features(const std::string& bam, const std::string& contig,
                                    int64_t start, int64_t end, int rows, int cols,
                                    int stride, int max_ins, uint32_t filter_flag,
-                                   int min_mapq, uint64_t seed) {
+                                   int min_mapq, uint64_t seed,
+                                   const std::string& sampler) {
     rk::FeatureParams P;
+    try {
+        P.sampler = rk::sampler_from_name(sampler);
+    } catch (const std::invalid_argument& e) {
+        throw py::value_error(e.what());
+    }
     P.rows = rows;
     P.cols = cols;
     P.stride = stride;
@@ -42,6 +48,38 @@ static py::tuple generate_features(const std::string& bam, const std::string& co
         std::memcpy(matrices.mutable_data(), res.matrices.data(), res.matrices.size());
     }
     return py::make_tuple(positions, matrices);
+}
+
+template <class T>
+static py::array_t<T> to_array(const std::vector<T>& v) {
+    auto a = py::array_t<T>(int64_t(v.size()));
+    if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
+    return a;
+}
+
+// Packed reads of a region for the device window builder (ops/windows.py).
+static py::dict region_reads(const std::string& bam, const std::string& contig,
+                             int64_t start, int64_t end, uint32_t filter_flag,
+                             int min_mapq, uint64_t seed) {
+    rk::RegionReads r;
+    {
+        py::gil_scoped_release release;
+        r = rk::region_reads(bam, contig, start, end, filter_flag,
+                             uint8_t(min_mapq), seed);
+    }
+    py::dict d;
+    d["ref_start"] = to_array(r.ref_start);
+    d["ref_end"] = to_array(r.ref_end);
+    d["reverse"] = to_array(r.reverse);
+    d["cigar_off"] = to_array(r.cigar_off);
+    d["seq_off"] = to_array(r.seq_off);
+    d["cigar"] = to_array(r.cigar);
+    d["seq4"] = to_array(r.seq4);
+    d["start"] = r.start;
+    d["end"] = r.end;
+    d["tid"] = r.tid;
+    d["region_key"] = r.region_key;
+    return d;
 }
 
 static py::list bam_references(const std::string& path) {
@@ -75,7 +113,10 @@ PYBIND11_MODULE(_pileup, m) {
           py::arg("start"), py::arg("end"), py::arg("rows") = 200, py::arg("cols") = 90,
           py::arg("stride") = 30, py::arg("max_ins") = 3,
           py::arg("filter_flag") = 0xf04u, py::arg("min_mapq") = 10,
-          py::arg("seed") = 0);
+          py::arg("seed") = 0, py::arg("sampler") = "mt19937");
+    m.def("region_reads", &region_reads, py::arg("bam"), py::arg("contig"),
+          py::arg("start"), py::arg("end"), py::arg("filter_flag") = 0xf04u,
+          py::arg("min_mapq") = 10, py::arg("seed") = 0);
     m.def("bam_references", &bam_references, py::arg("path"));
     m.def("fetch_records", &fetch_records, py::arg("path"), py::arg("contig"),
           py::arg("start"), py::arg("end"));

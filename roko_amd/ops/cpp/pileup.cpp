@@ -72,7 +72,59 @@ inline uint64_t mix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
+inline uint64_t region_key_of(uint64_t seed, int tid, int64_t start) {
+    return mix64(seed ^ mix64(uint64_t(tid) << 32 ^ uint64_t(start)));
+}
+
+// the one place the read filters live: extract_features and region_reads
+// must see the same reads in the same order
+inline bool keep_read(const BamRecord& rec, uint32_t filter_flag, uint8_t min_mapq) {
+    if (rec.flag & filter_flag) return false;
+    if ((rec.flag & FLAG_PAIRED) && !(rec.flag & FLAG_PROPER_PAIR)) return false;
+    if (rec.mapq < min_mapq) return false;
+    if (rec.l_seq <= 0 || rec.cigar.empty()) return false;
+    return true;
+}
+
 }  // namespace
+
+int sampler_from_name(const std::string& name) {
+    if (name == "mt19937") return SAMPLER_MT19937;
+    if (name == "counter") return SAMPLER_COUNTER;
+    throw std::invalid_argument("unknown sampler '" + name +
+                                "' (expected 'mt19937' or 'counter')");
+}
+
+RegionReads region_reads(const std::string& bam_path, const std::string& contig,
+                         int64_t start, int64_t end, uint32_t filter_flag,
+                         uint8_t min_mapq, uint64_t seed) {
+    BamReader bam(bam_path);
+    int tid = bam.tid_of(contig);
+    if (tid < 0) throw std::runtime_error("contig not in BAM header: " + contig);
+    int64_t ref_len = bam.references()[tid].length;
+    if (end > ref_len) end = ref_len;
+    if (start < 0) start = 0;
+    RegionReads out;
+    out.tid = tid;
+    out.start = start;
+    out.end = end;
+    out.region_key = region_key_of(seed, tid, start);
+    if (start >= end) return out;
+
+    bam.fetch(tid, start, end, [&](const BamRecord& rec) {
+        if (!keep_read(rec, filter_flag, min_mapq)) return;
+        out.ref_start.push_back(rec.pos);
+        out.ref_end.push_back(int32_t(rec.ref_end()));
+        out.reverse.push_back(rec.is_reverse() ? 1 : 0);
+        out.cigar.insert(out.cigar.end(), rec.cigar.begin(), rec.cigar.end());
+        out.seq4.insert(out.seq4.end(), rec.seq4.begin(), rec.seq4.end());
+        if (out.cigar.size() > 0xffffffffull || out.seq4.size() > 0xffffffffull)
+            throw std::runtime_error("region too large to pack (32-bit offsets)");
+        out.cigar_off.push_back(uint32_t(out.cigar.size()));
+        out.seq_off.push_back(uint32_t(out.seq4.size()));
+    });
+    return out;
+}
 
 FeatureResult extract_features(const std::string& bam_path, const std::string& contig,
                                int64_t start, int64_t end, const FeatureParams& P) {
@@ -92,10 +144,7 @@ FeatureResult extract_features(const std::string& bam_path, const std::string& c
 
     // ---- phase 1+2: fetch + CIGAR walk into the column store ----------------
     bam.fetch(tid, start, end, [&](const BamRecord& rec) {
-        if (rec.flag & P.filter_flag) return;
-        if ((rec.flag & FLAG_PAIRED) && !(rec.flag & FLAG_PROPER_PAIR)) return;
-        if (rec.mapq < P.min_mapq) return;
-        if (rec.l_seq <= 0 || rec.cigar.empty()) return;
+        if (!keep_read(rec, P.filter_flag, P.min_mapq)) return;
 
         uint32_t rid = uint32_t(reads.size());
         reads.push_back({rec.pos, rec.ref_end(), rec.is_reverse() ? STRAND_OFFSET : uint8_t(0)});
@@ -187,7 +236,9 @@ FeatureResult extract_features(const std::string& bam_path, const std::string& c
     std::deque<Key> queue;
 
     const int W = P.cols, R = P.rows, S = P.stride;
-    std::mt19937_64 rng(mix64(P.seed ^ mix64(uint64_t(tid) << 32 ^ uint64_t(start))));
+    const uint64_t region_key = region_key_of(P.seed, tid, start);
+    std::mt19937_64 rng(region_key);
+    const bool counter = P.sampler == SAMPLER_COUNTER;
 
     // scratch reused across windows
     std::vector<uint32_t> valid;                 // read ids with >=1 visible base
@@ -250,7 +301,13 @@ FeatureResult extract_features(const std::string& bam_path, const std::string& c
                 size_t xbase = out.matrices.size();
                 out.matrices.resize(xbase + size_t(R) * W);
                 for (int r = 0; r < R; ++r) {
-                    uint32_t pick = uint32_t(rng() % uint64_t(V));
+                    // window_id was advanced above: this window's ordinal
+                    // among all windows of the region is window_id - 1
+                    const uint64_t draw =
+                        counter ? mix64(region_key ^
+                                        mix64(uint64_t(window_id - 1) << 32 | uint64_t(r)))
+                                : rng();
+                    uint32_t pick = uint32_t(draw % uint64_t(V));
                     uint32_t rid = valid[pick];
                     const uint8_t off = reads[rid].offset;
                     const uint8_t* src = &dense[size_t(row_of[rid]) * W];

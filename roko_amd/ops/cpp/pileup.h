@@ -19,7 +19,22 @@ struct FeatureParams {
     uint32_t filter_flag = 0x4 | 0x100 | 0x200 | 0x400 | 0x800;
     uint8_t min_mapq = 10;
     uint64_t seed = 0;     // mixed with (contig, start) by the caller
+    // Row sampler. SAMPLER_MT19937 draws rng() % V from one mt19937_64 per
+    // region, consumed window after window (the default; its output is
+    // frozen). SAMPLER_COUNTER is stateless, so windows can be built in any
+    // order (the GPU builder, ops/hip/windows.hip, implements the same rule):
+    //   region_key = mix64(seed ^ mix64((tid << 32) ^ start))
+    //   draw(w, r) = mix64(region_key ^ mix64((w << 32) | r))
+    // row r of window w shows read valid[draw(w, r) % V], w counting every
+    // window of the region, skipped empty ones included.
+    int sampler = 0;
 };
+
+constexpr int SAMPLER_MT19937 = 0;
+constexpr int SAMPLER_COUNTER = 1;
+
+// "mt19937" / "counter" -> SAMPLER_*; throws std::invalid_argument otherwise.
+int sampler_from_name(const std::string& name);
 
 struct FeatureResult {
     int64_t n_windows = 0;
@@ -36,5 +51,25 @@ struct FeatureResult {
 // reference has undefined behaviour there, generate.cpp:123).
 FeatureResult extract_features(const std::string& bam_path, const std::string& contig,
                                int64_t start, int64_t end, const FeatureParams& params);
+
+// The filtered reads of a region, still packed as BAM stores them: what the
+// device window builder consumes. Same clamping, fetch, filters and read
+// order as phase 1 of extract_features; no CIGAR is walked here.
+struct RegionReads {
+    int64_t start = 0, end = 0;  // clamped region
+    int32_t tid = -1;
+    uint64_t region_key = 0;     // counter-sampler key of this region
+    std::vector<int32_t> ref_start;
+    std::vector<int32_t> ref_end;   // exclusive
+    std::vector<uint8_t> reverse;
+    std::vector<uint32_t> cigar_off{0};  // n + 1, in words
+    std::vector<uint32_t> seq_off{0};    // n + 1, in bytes
+    std::vector<uint32_t> cigar;         // len << 4 | op
+    std::vector<uint8_t> seq4;           // two bases per byte, high nibble first
+};
+
+RegionReads region_reads(const std::string& bam_path, const std::string& contig,
+                         int64_t start, int64_t end, uint32_t filter_flag,
+                         uint8_t min_mapq, uint64_t seed);
 
 }  // namespace rk

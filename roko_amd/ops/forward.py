@@ -256,6 +256,24 @@ class InferencePipeline:
         self._next += 1
         slot.submit_votes(n, table, n_slots, err_flag)
 
+    def submit_votes_device(self, x: torch.Tensor, pos: torch.Tensor, n: int,
+                            table: torch.Tensor, n_slots: int,
+                            err_flag: torch.Tensor) -> None:
+        """submit_votes() for windows that are already in device memory
+        (ops/windows.py): x (>=n, R, W) u8 and pos (>=n, W, 2) i32 on the
+        GPU, n <= batch. The slot copies them device to device on its own
+        stream, ordered behind the current stream, and keeps their memory
+        alive until the copy has run; no staging is involved."""
+        self._need_uncoalesced()
+        if not (x.is_cuda and pos.is_cuda):
+            raise ValueError("submit_votes_device takes device tensors; use "
+                             "votes_staging() + submit_votes() for host data")
+        if not 0 <= n <= min(self.batch, x.shape[0], pos.shape[0]):
+            raise ValueError(f"n={n} outside [0, min(batch, rows given)]")
+        slot = self.slots[self._next % self.depth]
+        self._next += 1
+        slot.submit_votes_device(x, pos, n, table, n_slots, err_flag)
+
     def _need_uncoalesced(self):
         if self.coalesce != 1:
             raise RuntimeError(
@@ -393,6 +411,23 @@ class _Slot:
         if getattr(self, "x_stage", None) is None:
             raise RuntimeError("call votes_staging() and fill it first")
         self.cpp.submit_votes(self.x_stage, self.pos_stage, n, table,
+                              n_slots, err_flag)
+
+    def submit_votes_device(self, x, pos, n: int, table, n_slots: int,
+                            err_flag):
+        if self.cpp is None:
+            raise RuntimeError(
+                "votes mode needs the C++ serving slot (ext.ServeSlot); it is "
+                "not available with ROKO_SERVE=graph or use_graphs=False")
+        if x.dtype != torch.uint8 or pos.dtype != torch.int32:
+            raise ValueError("x must be uint8 and pos int32")
+        if self.pending[0] is not None:
+            self.pending[0].materialize()
+            self.pending[0] = None
+        # the same back-pressure as the staging route: at most `depth`
+        # batches (and the window tensors they pin) are in flight
+        self.wait_done()
+        self.cpp.submit_votes(x.contiguous(), pos.contiguous(), n, table,
                               n_slots, err_flag)
 
     def submit(self, x: torch.Tensor, copy_out: bool, part: int = 0):

@@ -84,6 +84,25 @@ void vote_scatter(const uint8_t* preds, const int32_t* positions,
                   int n_cols, hipStream_t stream);
 void vote_consensus(const uint32_t* table, int64_t n_slots, uint8_t* maj,
                     hipStream_t stream);
+bool windows_geometry_ok(int rows, int cols, int stride, int max_ins);
+void windows_index(const int32_t* ref_start, const int32_t* ref_end,
+                   const uint8_t* reverse, const uint32_t* cigar_off,
+                   const uint32_t* seq_off, const uint32_t* cigar,
+                   const uint8_t* seq4, int32_t* op_rpos, int32_t* op_qpos,
+                   int n, int start, int end, int32_t* diff, int32_t* insd,
+                   int32_t* col0, int32_t* colpos, int ncols_max,
+                   int n_all_max, unsigned long long* mask, int32_t* wpre,
+                   int32_t* nvalid, int32_t* out_idx, int32_t* meta,
+                   hipStream_t stream);
+void windows_fill(const int32_t* ref_start, const int32_t* ref_end,
+                  const uint8_t* reverse, const uint32_t* cigar_off,
+                  const uint32_t* seq_off, const uint32_t* cigar,
+                  const uint8_t* seq4, int32_t* op_rpos, int32_t* op_qpos,
+                  int n, int start, int end, const int32_t* col0,
+                  const int32_t* colpos, const unsigned long long* mask,
+                  const int32_t* wpre, const int32_t* nvalid,
+                  const int32_t* out_idx, uint64_t region_key, int n_all,
+                  int n_out, uint8_t* x, int32_t* pos, hipStream_t stream);
 }  // namespace rk
 
 namespace {
@@ -692,6 +711,113 @@ void vote_consensus(torch::Tensor table, int64_t n_slots, torch::Tensor maj) {
 }
 
 // ---------------------------------------------------------------------------
+// Device window builder (windows.hip): a region's packed reads -> (x (n, 200,
+// 90) u8, pos (n, 90, 2) i32) on the current stream. The u32 offset and CIGAR
+// arrays arrive as int32 tensors holding the same bits (no first-class uint32
+// in torch); ops/windows.py has checked them against the array lengths.
+// `ncols_max` bounds the region's column count (the scratch is sized by it).
+// One 16-byte D2H read of the counts sits between the index kernels and the
+// fill, so the window tensor is allocated at its exact size.
+std::vector<torch::Tensor> build_windows(
+    torch::Tensor ref_start, torch::Tensor ref_end, torch::Tensor reverse,
+    torch::Tensor cigar_off, torch::Tensor seq_off, torch::Tensor cigar,
+    torch::Tensor seq4, int64_t start, int64_t end, uint64_t region_key,
+    int64_t ncols_max, int64_t rows, int64_t cols, int64_t stride,
+    int64_t max_ins) {
+    TORCH_CHECK(rk::windows_geometry_ok((int)rows, (int)cols, (int)stride,
+                                        (int)max_ins),
+                "build_windows is compiled for 200 rows x 90 columns, stride "
+                "30, 3 insertion slots");
+    check(ref_start, torch::kInt32, "ref_start");
+    check(ref_end, torch::kInt32, "ref_end");
+    check(reverse, torch::kUInt8, "reverse");
+    check(cigar_off, torch::kInt32, "cigar_off");
+    check(seq_off, torch::kInt32, "seq_off");
+    check(cigar, torch::kInt32, "cigar");
+    check(seq4, torch::kUInt8, "seq4");
+    const int64_t n = ref_start.numel();
+    TORCH_CHECK(ref_end.numel() == n && reverse.numel() == n &&
+                    cigar_off.numel() == n + 1 && seq_off.numel() == n + 1,
+                "per-read arrays disagree on the number of reads");
+    const int64_t L = end - start;
+    TORCH_CHECK(start >= 0 && L <= (int64_t(1) << 28) &&
+                    end < (int64_t(1) << 31),
+                "region out of range");
+    TORCH_CHECK(n < (int64_t(1) << 31) && cigar.numel() < (int64_t(1) << 31),
+                "too many reads or CIGAR ops in one region");
+    auto i32 = ref_start.options();
+    auto x = torch::empty({0, rows, cols}, reverse.options());
+    auto pos = torch::empty({0, cols, 2}, i32);
+    if (n == 0 || L <= 0 || cigar.numel() == 0) return {x, pos};
+    TORCH_CHECK(ncols_max >= 0 && ncols_max <= L * (max_ins + 1),
+                "ncols_max out of range");
+    const int64_t n_all_max =
+        ncols_max >= cols ? (ncols_max - cols) / stride + 1 : 0;
+    const int64_t nwords = (n + 63) / 64, ngroups = (n + 255) / 256;
+    TORCH_CHECK(n_all_max * ngroups < (int64_t(1) << 31),
+                "region too large for one window build");
+
+    auto op_rpos = torch::empty({cigar.numel()}, i32);
+    auto op_qpos = torch::empty({cigar.numel()}, i32);
+    auto zeros = torch::zeros({2 * L + 1 + 4}, i32);  // diff | insd | meta
+    auto col0 = torch::empty({L + 1}, i32);
+    auto colpos = torch::empty({std::max<int64_t>(ncols_max, 1)}, i32);
+    auto mask = torch::empty({std::max<int64_t>(n_all_max * nwords, 1)},
+                             i32.dtype(torch::kInt64));
+    auto wpre = torch::empty({std::max<int64_t>(n_all_max * nwords, 1)}, i32);
+    auto nvalid = torch::empty({std::max<int64_t>(n_all_max, 1)}, i32);
+    auto out_idx = torch::empty({std::max<int64_t>(n_all_max, 1)}, i32);
+    int32_t* diff = zeros.data_ptr<int32_t>();
+    int32_t* insd = diff + L + 1;
+    int32_t* meta = insd + L;
+    auto u32 = [](const torch::Tensor& t) {
+        return reinterpret_cast<const uint32_t*>(t.data_ptr<int32_t>());
+    };
+    auto mask_p =
+        reinterpret_cast<unsigned long long*>(mask.data_ptr<int64_t>());
+    hipStream_t s = cur_stream();
+    rk::windows_index(ref_start.data_ptr<int32_t>(),
+                      ref_end.data_ptr<int32_t>(), reverse.data_ptr<uint8_t>(),
+                      u32(cigar_off), u32(seq_off), u32(cigar),
+                      seq4.data_ptr<uint8_t>(), op_rpos.data_ptr<int32_t>(),
+                      op_qpos.data_ptr<int32_t>(), (int)n, (int)start,
+                      (int)end, diff, insd, col0.data_ptr<int32_t>(),
+                      colpos.data_ptr<int32_t>(), (int)ncols_max,
+                      (int)n_all_max, mask_p, wpre.data_ptr<int32_t>(),
+                      nvalid.data_ptr<int32_t>(), out_idx.data_ptr<int32_t>(),
+                      meta, s);
+    check_launch("window index kernels");
+    int32_t h[4];
+    hipError_t e = hipMemcpyAsync(h, meta, sizeof(h), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    TORCH_CHECK(e == hipSuccess, "window counts read-back: ",
+                hipGetErrorString(e));
+    TORCH_CHECK(!(h[3] & 2), "build_windows: the region has ", h[0],
+                " columns, more than the bound ", ncols_max);
+    TORCH_CHECK(!(h[3] & 1), "build_windows: zero-length CIGAR op in the "
+                "region; the device builder does not take such reads "
+                "(use the host extractor)");
+    const int64_t n_all = h[1], n_out = h[2];
+    TORCH_CHECK(n_all >= 0 && n_all <= n_all_max && n_out >= 0 &&
+                    n_out <= n_all, "window counts out of range");
+    if (n_out == 0) return {x, pos};
+    x = torch::empty({n_out, rows, cols}, reverse.options());
+    pos = torch::empty({n_out, cols, 2}, i32);
+    rk::windows_fill(ref_start.data_ptr<int32_t>(),
+                     ref_end.data_ptr<int32_t>(), reverse.data_ptr<uint8_t>(),
+                     u32(cigar_off), u32(seq_off), u32(cigar),
+                     seq4.data_ptr<uint8_t>(), op_rpos.data_ptr<int32_t>(),
+                     op_qpos.data_ptr<int32_t>(), (int)n, (int)start, (int)end,
+                     col0.data_ptr<int32_t>(), colpos.data_ptr<int32_t>(),
+                     mask_p, wpre.data_ptr<int32_t>(),
+                     nvalid.data_ptr<int32_t>(), out_idx.data_ptr<int32_t>(),
+                     region_key, (int)n_all, (int)n_out,
+                     x.data_ptr<uint8_t>(), pos.data_ptr<int32_t>(), s);
+    check_launch("window fill kernel");
+    return {x, pos};
+}
+
+// ---------------------------------------------------------------------------
 // Serving fast path: ONE C++ call enqueues the whole b-batch inference
 // forward on a slot-owned HIP stream.
 //
@@ -1230,6 +1356,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("err_flag"));
     m.def("vote_consensus", &vote_consensus, py::arg("table"),
           py::arg("n_slots"), py::arg("maj"));
+    m.def("build_windows", &build_windows, py::arg("ref_start"),
+          py::arg("ref_end"), py::arg("reverse"), py::arg("cigar_off"),
+          py::arg("seq_off"), py::arg("cigar"), py::arg("seq4"),
+          py::arg("start"), py::arg("end"), py::arg("region_key"),
+          py::arg("ncols_max"), py::arg("rows"), py::arg("cols"),
+          py::arg("stride"), py::arg("max_ins"));
     py::class_<ServeSlot>(m, "ServeSlot")
         .def(py::init<py::dict, int, torch::Tensor, int>(),
              py::arg("weights"), py::arg("batch"), py::arg("host_out"),

@@ -109,6 +109,16 @@ class DeviceVotes:
         self.pipe.submit_votes(n, self.table(contig), self.n_slots(contig),
                                self.err_flag)
 
+    def add_device_batch(self, contig: str, x: torch.Tensor,
+                         pos: torch.Tensor, n: int) -> None:
+        """Submit rows 0..n of device tensors x (>=n, R, W) u8 and pos (>=n,
+        W, 2) i32 (ops/windows.py), n <= the pipeline's batch. Nothing
+        crosses PCIe, so there is no host range check here: the vote kernel
+        drops and flags an out-of-range position, and `_check()` raises on
+        that flag before any table is read."""
+        self.pipe.submit_votes_device(x, pos, n, self.table(contig),
+                                      self.n_slots(contig), self.err_flag)
+
     def scatter(self, contig: str, preds, positions) -> None:
         """Add given predictions (N, W) u8 at positions (N, W, 2) i32 on the
         current stream. Rows with pos < 0 do not vote."""

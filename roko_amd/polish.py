@@ -1,7 +1,8 @@
 """One-command polish: draft FASTA + reads BAM + .pth -> polished FASTA.
 
   python -m roko_amd.polish <draft.fasta> <reads.bam> <model.pth> <out.fasta>
-      [--t workers] [--b batch] [--seed N]
+      [--t workers] [--b batch] [--seed N] [--extract host|device]
+      [--sampler mt19937|counter]
 
 Does what `features` followed by `inference` does, and writes the same FASTA
 byte for byte, without the RKW file between them: region windows stream from
@@ -10,6 +11,13 @@ vote happens on the device too (ops/votes.py) — predictions and vote tables
 never cross PCIe; one byte per column comes back per contig. Without a GPU
 the model's torch forward and the host vote tables are used, as in
 `inference.infer`.
+
+With --extract device the workers only inflate, filter and pack the reads
+(features.generate_reads); the windows are built on the GPU from those
+(ops/windows.py) and handed to the serving slots device to device, so no
+window ever exists on the host. That route samples rows with the counter
+sampler whatever --sampler says; `--extract host --sampler counter` writes
+the same FASTA.
 
 Single process only; for multi-GPU runs use `features` + `inference` under
 torchrun.
@@ -26,7 +34,7 @@ import numpy as np
 
 from . import config as C
 from .config import FeatureConfig
-from .features import generate_infer, generate_regions
+from .features import generate_infer, generate_reads, generate_regions
 from .io.fasta import read_fasta, write_fasta
 
 # NOTE: torch (and everything that imports it) is imported inside polish():
@@ -87,6 +95,27 @@ class _DeviceSink:
 
     def finish(self) -> Dict[str, str]:
         return {}
+
+
+class _DeviceBuildSink(_DeviceSink):
+    """Packed reads -> windows built on the GPU (ops/windows.py) -> serving
+    slots in votes mode, device to device, in slices of at most `batch`
+    windows. A region's last slice may be short."""
+
+    def __init__(self, model, batch, depth, lens, cfg, device):
+        super().__init__(model, batch, depth, lens)
+        self.cfg, self.device = cfg, device
+
+    def add_reads(self, contig: str, pack: dict) -> int:
+        from .ops.windows import build_windows
+
+        x, pos = build_windows(pack, self.cfg, self.device)
+        n = int(x.shape[0])
+        for off in range(0, n, self.batch):
+            k = min(self.batch, n - off)
+            self.dv.add_device_batch(contig, x[off : off + k],
+                                     pos[off : off + k], k)
+        return n
 
 
 class _HostSink:
@@ -158,12 +187,26 @@ def polish(
     model=None,
     log=print,
     depth: int = 16,
+    extract: str = "host",
 ) -> Dict[str, str]:
     """Polish `draft_fasta` with the reads in `reads_bam`; returns {contig:
     polished sequence} and writes FASTA if `out_fasta` is given. Regions,
     FeatureConfig and seeding are those of `features.run`; `depth` is the
-    number of in-flight batches on the GPU."""
+    number of in-flight batches on the GPU. `extract="device"` builds the
+    windows on the GPU from packed reads (counter sampler, whatever
+    `cfg.sampler` says); it needs a GPU."""
     cfg = cfg or FeatureConfig()
+    if extract not in ("host", "device"):
+        raise ValueError(f"extract must be 'host' or 'device', got {extract!r}")
+    if extract == "device":
+        from .ops.windows import check_geometry
+
+        dev_type = _device_type(device)
+        if dev_type != "cuda":
+            raise ValueError(
+                "extract='device' builds the windows on the GPU and needs a "
+                f"GPU device (got {dev_type!r}); use extract='host'")
+        check_geometry(cfg)
     refs = list(read_fasta(draft_fasta))
     jobs = []
     for name, seq in refs:
@@ -179,15 +222,24 @@ def polish(
         pool = multiprocessing.get_context("spawn").Pool(processes=workers)
     try:
         return _polish(refs, jobs, pool, model_path, out_fasta, workers,
-                       batch_size, device, model, log, depth)
+                       batch_size, device, model, log, depth, extract, cfg)
     finally:
         if pool is not None:
             pool.terminate()
             pool.join()
 
 
+def _device_type(device) -> str:
+    """Type of the device polish() would run on, without creating it."""
+    import torch
+
+    if device is None:
+        return "cuda" if torch.cuda.is_available() else "cpu"
+    return torch.device(device).type
+
+
 def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
-            device, model, log, depth) -> Dict[str, str]:
+            device, model, log, depth, extract, cfg) -> Dict[str, str]:
     import torch
 
     from .model import RokoModel
@@ -201,19 +253,23 @@ def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
     model = model.to(device).eval()
 
     drafts = dict(refs)
-    if device.type == "cuda":
+    if extract == "device":
+        sink = _DeviceBuildSink(model, batch_size, depth,
+                                {n: len(s) for n, s in refs}, cfg, device)
+    elif device.type == "cuda":
         sink = _DeviceSink(model, batch_size, depth,
                            {n: len(s) for n, s in refs})
     else:
         sink = _HostSink(model, batch_size, device, drafts)
+    worker = generate_reads if extract == "device" else generate_infer
     log(f"polish: {len(jobs)} region jobs, {workers} workers, "
-        f"batch {batch_size}, votes on {device.type}")
+        f"batch {batch_size}, windows on {extract}, votes on {device.type}")
 
     out: Dict[str, str] = {}
     n_windows = n_errors = 0
     t0 = time.time()
-    results = (pool.imap(generate_infer, jobs) if pool is not None
-               else map(generate_infer, jobs))
+    results = (pool.imap(worker, jobs) if pool is not None
+               else map(worker, jobs))
     current = None  # contig being consumed; jobs are in contig order
     for result, job in zip(results, jobs):
         contig = job[1]
@@ -227,12 +283,15 @@ def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
             # same fence as features.run: one in-parent retry, then skip
             log(f"WARNING: region {result[1]} failed: {result[2]} "
                 "(retrying once)")
-            result = generate_infer(job)
+            result = worker(job)
             if result[0] == "__error__":
                 n_errors += 1
                 log(f"WARNING: region {result[1]} failed twice: "
                     f"{result[2]} (skipped)")
                 continue
+        if extract == "device":
+            n_windows += sink.add_reads(contig, result[3])
+            continue
         _, _, _, positions, examples, _ = result
         sink.add(contig, positions, examples)
         n_windows += len(positions)
@@ -267,9 +326,16 @@ def main(argv=None):
                    help="extractor worker processes (they never use the GPU)")
     p.add_argument("--b", type=int, default=C.BATCH_SIZE, help="batch size")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--extract", choices=("host", "device"), default="host",
+                   help="where windows are built: extractor workers (host) "
+                        "or the GPU, from packed reads (device)")
+    p.add_argument("--sampler", choices=("mt19937", "counter"),
+                   default="mt19937",
+                   help="row sampler of --extract host (device: counter)")
     a = p.parse_args(argv)
     polish(a.draft, a.bam, a.model, a.out, workers=a.t, batch_size=a.b,
-           cfg=FeatureConfig(seed=a.seed))
+           cfg=FeatureConfig(seed=a.seed, sampler=a.sampler),
+           extract=a.extract)
 
 
 if __name__ == "__main__":

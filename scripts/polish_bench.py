@@ -1,7 +1,8 @@
-"""End-to-end polishing rate: draft + BAM -> FASTA, three ways.
+"""End-to-end polishing rate: draft + BAM -> FASTA, five ways.
 
   python scripts/polish_bench.py [--ref-len N] [--cov C] [--t WORKERS]
-      [--b BATCH] [--limit SECONDS] [--dir DIR]
+      [--b BATCH] [--limit SECONDS] [--dir DIR] [--routes a,b,...]
+      [--repeat N]
 
 Builds a synthetic assembly (the generators of tests/test_gpu_e2e.py::
 _make_case, size given by --ref-len), then times
@@ -9,12 +10,19 @@ _make_case, size given by --ref-len), then times
   two_step      features -> RKW file -> infer(votes="host")
   infer_device  features -> RKW file -> infer(votes="device")
   polish        roko_amd.polish.polish (no file, votes on the device)
+  polish_host_counter   polish with the counter row sampler
+  polish_device         polish(extract="device"): workers pack reads, the
+                        windows are built on the GPU (counter sampler)
+
+--routes picks a subset; --repeat N runs the chosen routes N times in turn
+(a, b, a, b, ...), so that drift of the machine hits all of them alike.
 
 Each way runs in a process of its own under `timeout` (--limit seconds), so
 one that hangs or faults ends there and nothing is started after it. Each
 prints one JSON line: wall time, windows/s, bases/s (draft bases per second
 of wall time), and for the file routes the split between extraction and
-inference. A last line says whether the three FASTA files are identical.
+inference. A last line says whether the FASTA files of the routes that ran
+are identical within each sampler (the two samplers draw different rows).
 The model is randomly initialised: rates do not depend on the weights.
 """
 
@@ -30,6 +38,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEPS = ("two_step", "infer_device", "polish")
+COUNTER_STEPS = ("polish_host_counter", "polish_device")
+ALL_STEPS = STEPS + COUNTER_STEPS
 
 
 def make_case(d, ref_len, cov, seed=7):
@@ -74,11 +84,14 @@ def run_step(step, d, workers, batch, region):
     rec = {"step": step, "workers": workers, "batch": batch,
            "draft_bases": draft_bases}
     t0 = time.time()
-    if step == "polish":
+    if step.startswith("polish"):
         from roko_amd.polish import LAST_RUN
 
+        if step != "polish":
+            cfg.sampler = "counter"
         polish(draft, bam, ckpt, out, workers=workers, batch_size=batch,
-               cfg=cfg, log=quiet)
+               cfg=cfg, log=quiet,
+               extract="device" if step == "polish_device" else "host")
         n = LAST_RUN["windows"]
     else:
         rkw = os.path.join(d, f"{step}.rkw")
@@ -107,7 +120,11 @@ def main():
     p.add_argument("--limit", type=int, default=240,
                    help="time limit per route, seconds")
     p.add_argument("--dir", default=None, help="work directory")
-    p.add_argument("--step", choices=STEPS, default=None,
+    p.add_argument("--routes", default=",".join(ALL_STEPS),
+                   help="comma-separated routes to run, in this order")
+    p.add_argument("--repeat", type=int, default=1,
+                   help="run the chosen routes this many times, in turn")
+    p.add_argument("--step", choices=ALL_STEPS, default=None,
                    help="(internal) run one route in this process")
     a = p.parse_args()
     if a.step:
@@ -126,7 +143,11 @@ def main():
     torch.save(RokoModel().state_dict(), os.path.join(d, "model.pth"))
     print(json.dumps({"step": "make_case", "draft_bases": n,
                       "wall_s": round(time.time() - t0, 1)}), flush=True)
-    for step in STEPS:
+    routes = [r for r in a.routes.split(",") if r]
+    for r in routes:
+        if r not in ALL_STEPS:
+            p.error(f"unknown route {r!r} (known: {', '.join(ALL_STEPS)})")
+    for step in routes * max(a.repeat, 1):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable,
                os.path.abspath(__file__), "--step", step, "--dir", d,
                "--t", str(a.t), "--b", str(a.b), "--region", str(a.region)]
@@ -134,10 +155,14 @@ def main():
         if rc != 0:
             print(json.dumps({"step": step, "failed": rc}), flush=True)
             sys.exit(rc)  # start nothing more after a failure
-    blobs = [open(os.path.join(d, f"{s}.fasta"), "rb").read() for s in STEPS]
-    print(json.dumps({"step": "compare",
-                      "identical": blobs[0] == blobs[1] == blobs[2]}),
-          flush=True)
+    rec = {"step": "compare"}
+    for key, group in (("identical", STEPS),
+                       ("identical_counter", COUNTER_STEPS)):
+        blobs = {open(os.path.join(d, f"{s}.fasta"), "rb").read()
+                 for s in group if s in routes}
+        if blobs:
+            rec[key] = len(blobs) == 1
+    print(json.dumps(rec), flush=True)
 
 
 if __name__ == "__main__":
