@@ -19,8 +19,10 @@ from .. import config as C
 #: through the 12 base classes — ~2.3x fewer MFMAs per column) does ~1.45x
 #: less chip-work than the shared train-front kernel; v3 (wave-private
 #: columns, no per-phase barriers) is the measured-fastest default
-#: (106.7 us vs v2's 152.4 at b=128). ROKO_FRONT=v2/v1/shared for A/B.
-_FRONT = os.environ.get("ROKO_FRONT", "v3")
+#: (106.7 us vs v2's 152.4 at b=128). v4 is v3's arithmetic, byte for byte,
+#: on a persistent grid at three waves per SIMD with W1 in LDS and the
+#: G1->G2->G3 hand-offs in registers. ROKO_FRONT=v4/v3/v2/v1/shared for A/B.
+_FRONT = os.environ.get("ROKO_FRONT", "v4")
 
 
 def _front_eval(ext, ids, w):
@@ -30,6 +32,9 @@ def _front_eval(ext, ids, w):
     if _FRONT == "v1" or not hasattr(ext, "embed_mlp_fwd2"):
         return ext.embed_mlp_fwd(ids, w["w1"], w["b1"], w["w2"], w["b2"],
                                  w["emb"])
+    if _FRONT == "v4":
+        return ext.embed_mlp_fwd4(ids, w["w1g"], w["b1"], w["w2"], w["b2"],
+                                  w["emb"])
     if _FRONT == "v3" and hasattr(ext, "embed_mlp_fwd3"):
         return ext.embed_mlp_fwd3(ids, w["w1g"], w["b1"], w["w2"], w["b2"],
                                   w["emb"])

@@ -24,6 +24,11 @@ void embed_mlp_fwd3(const uint8_t* ids, const void* w1g, const float* b1,
                     const void* w2, const float* b2, const void* emb,
                     void* out, int B, hipStream_t stream,
                     unsigned long long* timing, int ldo = 500);
+void embed_mlp_fwd4(const uint8_t* ids, const void* w1g, const float* b1,
+                    const void* w2, const float* b2, const void* emb,
+                    void* out, int B, hipStream_t stream,
+                    unsigned long long* timing, int ldo = 500,
+                    int max_blocks = 0);
 void gru_layer_fwd(const void* xg, const void* u, const float* bhh, void* hseq,
                    void* cache, int T, int B, hipStream_t stream, uint32_t dbg);
 void gru_layer_fwd_fused(const void* x, const void* w_ih_p, const void* b_ih,
@@ -176,13 +181,16 @@ torch::Tensor embed_mlp_fwd2(torch::Tensor ids, torch::Tensor w1g,
     return out;
 }
 
-// same contract as embed_mlp_fwd2, wave-private-column kernel (v3)
-torch::Tensor embed_mlp_fwd3(torch::Tensor ids, torch::Tensor w1g,
-                             torch::Tensor b1, torch::Tensor w2,
-                             torch::Tensor b2, torch::Tensor emb,
-                             c10::optional<torch::Tensor> timing = c10::nullopt,
-                             int64_t ldo = 500,
-                             c10::optional<torch::Tensor> out_ = c10::nullopt) {
+// same contract as embed_mlp_fwd2, wave-private-column kernels: v3 (one
+// wave per SIMD, `version` 3) and v4 (persistent, three waves per SIMD)
+torch::Tensor front_wave_private(int version, torch::Tensor ids,
+                                 torch::Tensor w1g, torch::Tensor b1,
+                                 torch::Tensor w2, torch::Tensor b2,
+                                 torch::Tensor emb,
+                                 c10::optional<torch::Tensor> timing,
+                                 int64_t ldo,
+                                 c10::optional<torch::Tensor> out_,
+                                 int64_t max_blocks) {
     check(ids, torch::kUInt8, "ids");
     check(w1g, torch::kBFloat16, "w1g");
     check(b1, torch::kFloat32, "b1");
@@ -208,15 +216,46 @@ torch::Tensor embed_mlp_fwd3(torch::Tensor ids, torch::Tensor w1g,
     } else {
         out = torch::zeros({90, B, ldo}, ids.options().dtype(torch::kBFloat16));
     }
-    rk::embed_mlp_fwd3(ids.data_ptr<uint8_t>(), w1g.data_ptr(),
-                       b1.data_ptr<float>(), w2.data_ptr(),
-                       b2.data_ptr<float>(), emb.data_ptr(), out.data_ptr(),
-                       B, cur_stream(),
-                       timing ? reinterpret_cast<unsigned long long*>(
-                                    timing->data_ptr<int64_t>())
-                              : nullptr,
-                       (int)ldo);
+    unsigned long long* tim =
+        timing ? reinterpret_cast<unsigned long long*>(
+                     timing->data_ptr<int64_t>())
+               : nullptr;
+    if (version == 4)
+        rk::embed_mlp_fwd4(ids.data_ptr<uint8_t>(), w1g.data_ptr(),
+                           b1.data_ptr<float>(), w2.data_ptr(),
+                           b2.data_ptr<float>(), emb.data_ptr(),
+                           out.data_ptr(), B, cur_stream(), tim, (int)ldo,
+                           (int)max_blocks);
+    else
+        rk::embed_mlp_fwd3(ids.data_ptr<uint8_t>(), w1g.data_ptr(),
+                           b1.data_ptr<float>(), w2.data_ptr(),
+                           b2.data_ptr<float>(), emb.data_ptr(),
+                           out.data_ptr(), B, cur_stream(), tim, (int)ldo);
     return out;
+}
+
+torch::Tensor embed_mlp_fwd3(torch::Tensor ids, torch::Tensor w1g,
+                             torch::Tensor b1, torch::Tensor w2,
+                             torch::Tensor b2, torch::Tensor emb,
+                             c10::optional<torch::Tensor> timing = c10::nullopt,
+                             int64_t ldo = 500,
+                             c10::optional<torch::Tensor> out_ = c10::nullopt) {
+    return front_wave_private(3, ids, w1g, b1, w2, b2, emb, timing, ldo, out_,
+                              0);
+}
+
+// max_blocks > 0 caps the persistent grid (tests: several windows per
+// workgroup at a small batch)
+torch::Tensor embed_mlp_fwd4(torch::Tensor ids, torch::Tensor w1g,
+                             torch::Tensor b1, torch::Tensor w2,
+                             torch::Tensor b2, torch::Tensor emb,
+                             c10::optional<torch::Tensor> timing = c10::nullopt,
+                             int64_t ldo = 500,
+                             c10::optional<torch::Tensor> out_ = c10::nullopt,
+                             int64_t max_blocks = 0) {
+    TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
+    return front_wave_private(4, ids, w1g, b1, w2, b2, emb, timing, ldo, out_,
+                              max_blocks);
 }
 
 // Serving fused variant: x (T, B, IN) bf16 + row-padded W_ih (768, KP) +
@@ -828,6 +867,9 @@ std::vector<torch::Tensor> build_windows(
 // threads do not help (a runtime-global lock serializes enqueue). Replacing
 // the per-batch Python/graph work with one pybind call of direct kernel
 // enqueues cuts the host cost to the raw HIP launches.
+// default of ROKO_FRONT: v4 (true) or v3
+constexpr bool FRONT_V4_DEFAULT = true;
+
 struct ServeSlot {
     // weights (kernel-ready layouts from roko_amd.ops.forward._bf16_weights)
     torch::Tensor w1, b1, w2, b2, emb, w4, b4;
@@ -855,11 +897,18 @@ struct ServeSlot {
     int unlaunched_parts = 0;
     at::cuda::CUDAStream stream;
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
-    // front kernel choice (ROKO_FRONT env; v3 default — measured 22.7M vs
-    // 19.8M bases/s serving with v2, bit-exact)
+    // front kernel choice (ROKO_FRONT env; v3 measured 22.7M vs 19.8M
+    // bases/s serving with v2, bit-exact). use_v3 covers both wave-private
+    // kernels (they share the ldo contract); use_v4 picks the persistent
+    // three-waves-per-SIMD one, byte-identical to v3 (ROKO_FRONT=v3 for A/B)
     bool use_v3 = [] {
         const char* f = getenv("ROKO_FRONT");
         return !(f && std::string(f) == "v2");
+    }();
+    bool use_v4 = [] {
+        const char* f = getenv("ROKO_FRONT");
+        return FRONT_V4_DEFAULT ? !(f && std::string(f) != "v4")
+                                : (f && std::string(f) == "v4");
     }();
     // xg-GEMM fold into the GRU kernel (ROKO_XGFOLD=1 to enable for A/B)
     bool use_fold = [] {
@@ -983,7 +1032,12 @@ struct ServeSlot {
     // is a raw kernel enqueue on `s`, so the sequence is hipGraph
     // capture-legal. Callers guarantee use_fold || xg2_path.
     void enqueue_model(hipStream_t s) {
-        if (w1gt.defined() && use_v3)
+        if (w1gt.defined() && use_v3 && use_v4)
+            rk::embed_mlp_fwd4(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
+                               b1.data_ptr<float>(), w2.data_ptr(),
+                               b2.data_ptr<float>(), emb.data_ptr(),
+                               seq.data_ptr(), B, s, nullptr, seq_ld);
+        else if (w1gt.defined() && use_v3)
             rk::embed_mlp_fwd3(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
                                b1.data_ptr<float>(), w2.data_ptr(),
                                b2.data_ptr<float>(), emb.data_ptr(),
@@ -1066,7 +1120,12 @@ struct ServeSlot {
     // not cover): front -> 3x(addmm + GRU) -> head. The caller holds a
     // CUDAStreamGuard on the slot stream for addmm_out.
     void enqueue_model_lt(hipStream_t s) {
-        if (w1gt.defined() && use_v3)
+        if (w1gt.defined() && use_v3 && use_v4)
+            rk::embed_mlp_fwd4(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
+                               b1.data_ptr<float>(), w2.data_ptr(),
+                               b2.data_ptr<float>(), emb.data_ptr(),
+                               seq.data_ptr(), B, s, nullptr);
+        else if (w1gt.defined() && use_v3)
             rk::embed_mlp_fwd3(x_buf.data_ptr<uint8_t>(), w1gt.data_ptr(),
                                b1.data_ptr<float>(), w2.data_ptr(),
                                b2.data_ptr<float>(), emb.data_ptr(),
@@ -1308,6 +1367,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("emb"),
           py::arg("timing") = c10::nullopt, py::arg("ldo") = 500,
           py::arg("out") = c10::nullopt);
+    m.def("embed_mlp_fwd4", &embed_mlp_fwd4, py::arg("ids"), py::arg("w1g"),
+          py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("emb"),
+          py::arg("timing") = c10::nullopt, py::arg("ldo") = 500,
+          py::arg("out") = c10::nullopt, py::arg("max_blocks") = 0);
     m.def("embed_mlp_fwd", &embed_mlp_fwd, py::arg("ids"), py::arg("w1"),
           py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("emb"),
           py::arg("dbg") = 0, py::arg("timing") = c10::nullopt);

@@ -10,7 +10,8 @@
 // the per-column MAC count ~8x (200->12 contraction) and turns the gather
 // into a 200-entry scatter of ones. Exact in eval mode (no dropout).
 //
-// TWO kernels live in this file. The first (v1) is the per-column version:
+// FOUR kernels live in this file (v1-v4; v4 is the default, see its note
+// below). The first (v1) is the per-column version:
 // one workgroup (eight waves, two per SIMD) owns one window, waves 0-3 run
 // column w and waves 4-7 column w+1 with private hot/a/t1/t2 tiles. It is
 // KEPT as the reference implementation and A/B fallback (ROKO_FRONT=v1):
@@ -457,9 +458,14 @@ __global__ __launch_bounds__(512, 2) void embed_mlp_fwd2_kernel(
 // whole column with PRIVATE hot/a/t1/t2 tiles — there is no barrier between
 // G1/G2/G3 at all (within-wave lgkmcnt ordering is free), so a wave streams
 // 93 MFMAs per column back to back with register prefetch across phases.
-// 4 waves per workgroup (LDS: 4 x ~35 KB private + ~9 KB shared = 148 KB);
-// W1 A-fragments come straight from L2 like v2's P1. One wave per SIMD —
-// the stream is MFMA-ILP-rich, so no partner wave is needed for cover.
+// 4 waves per workgroup (LDS: 4 x ~35 KB private + ~9 KB shared = 148 KB),
+// one wave per SIMD. The G1 loop below asks for W1 A-fragments from global
+// memory per column, but that is not what runs: the compiler hoists all 49
+// loads in front of the column loop, W1 sits in 196 accumulation registers
+// (426 registers in all) and every column copies it back with 242
+// v_accvgpr_read. ~1,080 instructions per column for 93 MFMAs with no
+// partner wave to cover them — what v4 below removes. Kept as the A/B
+// partner (ROKO_FRONT=v3) and the byte-exact reference of v4's tests.
 namespace v3 {
 
 constexpr int WAVES3 = 4;
@@ -570,10 +576,9 @@ __global__ __launch_bounds__(WAVES3 * 64, 1) void embed_mlp_fwd3_kernel(
 
         // ---- G1: A = W1 · Hot  (7 m-tiles x 7 k-steps, 49 MFMA) -----------
         // 7 independent accumulator chains; B-frag per k shared across m.
-        // THREE-deep k-window: at one wave per SIMD the register budget is
-        // 512/lane, so ~21 L2 A-fragments stay in flight — ~2 k-steps
-        // (~240 MFMA cycles) of cover for the ~200-cycle L2 latency (the
-        // 1-deep window measured neutral: 7 MFMAs of cover was not enough).
+        // Written as a three-deep k-window of global loads; the compiler
+        // sees that the loads are column-invariant and hoists all 49 out
+        // of the column loop (note above), so the window is moot.
         {
             f32x4 acc[7];
 #pragma unroll
@@ -701,6 +706,313 @@ __global__ __launch_bounds__(WAVES3 * 64, 1) void embed_mlp_fwd3_kernel(
 }
 
 }  // namespace v3
+
+// ---------------------------------------------------------------------------
+// v4: v3's wave-private columns at THREE waves per SIMD, with every tile
+// that kept v3 at one wave per SIMD taken out of LDS. v3's column loop is ~1,080
+// instructions for 93 MFMAs: a lone in-order wave spends its time issuing
+// accvgpr copies, epilogue VALU and LDS round trips with no partner wave to
+// cover them. Here
+//   * the grid is PERSISTENT (min(B, CUs) workgroups of 12 waves); W1 is
+//     staged once per CU into LDS (pitch 240: 480 B = 30 16-B slots, and
+//     30 mod 16 = 2*odd keeps the four 16-lane ds_read_b128 groups
+//     conflict-free — the global image's 464 B pitch is 2-way) and the
+//     (window, column) items of the workgroup's windows are dealt round-robin
+//     to the waves, so the 90 % 12 tail is paid once per workgroup;
+//   * G1 runs with swapped operands (hot as A, W1 as B; both fragment
+//     layouts are the same, every output keeps its k order), so a lane holds
+//     a[f = 16mt + lcol][c = 4lrow + i]; G2 wants a[f][c = 8lrow + j]. Two
+//     half exchanges per dword (v_permlane32_swap, then v_permlane16_swap)
+//     turn one into the other in registers: there is no `a` tile;
+//   * the same exchange turns G2's packed C layout (f = 16mt + 4lrow + i)
+//     into G3's B operand (f = 32kb + 8lrow + j): there is no t1 tile, and
+//     G2/G3 run per n-tile, so 28 accumulators are live instead of 112;
+//   * relu is one packed 16-bit integer max per bf16 pair after rounding
+//     (bf16 rounding is monotone and sign-preserving, -0 -> +0 like fmaxf).
+// What is left in LDS per wave is the one-hot tile (12 live rows + one zero
+// row that lanes lcol >= 12 read) and the 1 KB output staging row.
+// Arithmetic is v3's: same MFMA, same k order per output, fp32 bias add,
+// relu, one bf16 round — the output equals v3's byte for byte.
+namespace v4 {
+
+constexpr int WAVES4 = 12;   // three per SIMD: 142 VGPRs, 138 KB LDS (eight
+                             // waves measured 6% slower at B = 1024)
+constexpr int W1_LD = 240;   // LDS pitch of W1 and the hot tile (elements)
+constexpr int HOT_ROWS = 13; // 12 classes + the zero row
+
+using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+using s16x2 = __attribute__((ext_vector_type(2))) short;
+
+// two floats -> one dword of two bf16 (round to nearest even, lo = a)
+RK_DEV unsigned int pack_bf16(float a, float b) {
+    const bf16x2 p = __builtin_convertvector(f32x2{a, b}, bf16x2);
+    return __builtin_bit_cast(unsigned int, p);
+}
+
+// relu on a packed bf16 pair: signed 16-bit max against 0
+RK_DEV unsigned int relu_pk(unsigned int v) {
+    const s16x2 r = __builtin_elementwise_max(__builtin_bit_cast(s16x2, v),
+                                              s16x2{0, 0});
+    return __builtin_bit_cast(unsigned int, r);
+}
+
+// Rows are the four 16-lane groups of the wave. In: x = (x0,x1,x2,x3),
+// y = (y0,y1,y2,y3) by row. Out: x = (x0,x2,y0,y2), y = (x1,x3,y1,y3).
+// permlane32_swap exchanges x's rows 2,3 with y's rows 0,1; permlane16_swap
+// then exchanges x's odd rows with y's even rows.
+RK_DEV void row_exchange(unsigned int& x, unsigned int& y) {
+    u32x2 r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+    r = __builtin_amdgcn_permlane16_swap(r[0], r[1], false, false);
+    x = r[0];
+    y = r[1];
+}
+
+// Two packed C-layout m-tiles (rows 16mt + 4lrow + i; lo = i 0,1, hi = i
+// 2,3) -> the 16x16x32 operand fragment over the 32 rows of both tiles
+// (rows 8lrow + j). p1 is the tile of rows 16..31.
+RK_DEV bf16x8 c_to_frag(unsigned int p0lo, unsigned int p0hi,
+                        unsigned int p1lo, unsigned int p1hi) {
+    row_exchange(p0lo, p1lo);
+    row_exchange(p0hi, p1hi);
+    return __builtin_bit_cast(bf16x8, u32x4{p0lo, p0hi, p1lo, p1hi});
+}
+
+__global__ __launch_bounds__(WAVES4 * 64, 1) void embed_mlp_fwd4_kernel(
+    const uint8_t* __restrict__ ids,  // (B, R, W)
+    const bf16* __restrict__ w1g,     // (MP=112, KP_LD=232) zero-padded W1
+    const float* __restrict__ b1,     // (F1)
+    const bf16* __restrict__ w2,      // (F2, F1)
+    const float* __restrict__ b2,     // (F2)
+    const bf16* __restrict__ emb,     // (12, E)
+    bf16* __restrict__ out,           // (W, B, ldo): cols [0, OUT) written
+    int B,
+    int ldo,                          // output row stride (elements, % 8 == 0
+                                      // or 500)
+    unsigned long long* __restrict__ timing) {  // optional (4): per-phase
+                                                // cycle sums from lane 0
+    __shared__ struct {
+        bf16 w1s[MP][W1_LD];                   // G1 B-operand, staged once
+        bf16 hot_t[WAVES4][HOT_ROWS][W1_LD];   // G1 A-operand [cls][k=r]
+        unsigned int t2[WAVES4][256];          // output staging (bf16 pairs)
+    } lds;
+
+    const int tid = threadIdx.x;
+    const int wid = tid >> 6;
+    const int lane = tid & 63;
+    const int lrow = lane >> 4;
+    const int lcol = lane & 15;
+
+    // ---- one-time staging -------------------------------------------------
+    // W1: 112 rows x 28 16-byte chunks (k < 224; nothing reads past it)
+    for (int e = tid; e < MP * 28; e += WAVES4 * 64) {
+        const int row = e / 28, ch = e - row * 28;
+        *reinterpret_cast<bf16x8*>(&lds.w1s[row][ch * 8]) =
+            *reinterpret_cast<const bf16x8*>(w1g + row * KP_LD + ch * 8);
+    }
+    // hot tiles zeroed whole once (k pad 200..223 and the zero row stay 0;
+    // the un-scatter below re-zeroes exactly the entries a column set)
+    for (int e = tid; e < WAVES4 * HOT_ROWS * W1_LD / 2; e += WAVES4 * 64)
+        reinterpret_cast<unsigned int*>(&lds.hot_t[0][0][0])[e] = 0u;
+
+    // loop-invariant operand fragments + biases, register-resident: read
+    // from global once per workgroup, zero outside the live range
+    bf16x8 e_bv[4], w2_av[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int e = nt * 16 + lcol, c = 8 * lrow + j;
+            const bf16 v = (e < E && c < 12) ? emb[c * E + e] : f2bf(0.f);
+            e_bv[nt][j] = __builtin_bit_cast(__bf16, v);
+        }
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int f = kb * 32 + 8 * lrow + j;
+            const bf16 v = (lcol < F2 && f < F1) ? w2[lcol * F1 + f]
+                                                 : f2bf(0.f);
+            w2_av[kb][j] = __builtin_bit_cast(__bf16, v);
+        }
+    float b1r[7][4], b2r[4];
+#pragma unroll
+    for (int mt = 0; mt < 7; ++mt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int f = mt * 16 + lrow * 4 + i;
+            b1r[mt][i] = (f < F1) ? b1[f] : 0.f;
+        }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        b2r[i] = (lrow * 4 + i < F2) ? b2[lrow * 4 + i] : 0.f;
+    __syncthreads();  // the ONLY barrier (staging); columns are wave-private
+
+    bf16(&hot)[HOT_ROWS][W1_LD] = lds.hot_t[wid];
+    unsigned int* t2 = lds.t2[wid];
+    // lanes lcol >= 12 read the zero row: classes 12..15 do not exist
+    const bf16* hotp = &hot[lcol < 12 ? lcol : 12][8 * lrow];
+    const bf16* w1p = &lds.w1s[lcol][8 * lrow];
+
+    // this workgroup's windows are blockIdx.x, + gridDim.x, ...; their
+    // columns form one item list dealt round-robin to the waves
+    const int nwin = (B - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int nitems = nwin * W;
+
+    // ids of one item: lane holds reads lane, +64, +128 (+192 for lane < 8)
+    auto load_ids = [&](int t, unsigned int (&id)[4]) {
+        const int n = t / W, w = t - n * W;
+        const uint8_t* col =
+            ids + ((size_t)blockIdx.x + (size_t)n * gridDim.x) * R * W + w;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = lane + q * 64;
+            id[q] = (r < R) ? col[(size_t)r * W] : 255u;
+        }
+    };
+
+    unsigned long long tacc[4] = {0, 0, 0, 0};
+#define V4_T0 unsigned long long tp0 = (timing && tid == 0) \
+        ? __builtin_amdgcn_s_memtime() : 0
+#define V4_T1(i) if (timing && tid == 0) { \
+        unsigned long long tn = __builtin_amdgcn_s_memtime(); \
+        tacc[i] += tn - tp0; tp0 = tn; }
+
+    unsigned int cur[4];
+    if (wid < nitems) load_ids(wid, cur);
+    for (int t = wid; t < nitems; t += WAVES4) {
+        const int n = t / W, w = t - n * W;
+        const int b = blockIdx.x + n * gridDim.x;
+        V4_T0;
+        // ---- scatter: 200 one-hots ----------------------------------------
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (cur[q] < 12) hot[cur[q]][lane + q * 64] = f2bf(1.0f);
+        // the next item's ids travel under this item's MFMAs
+        unsigned int nxt[4] = {255u, 255u, 255u, 255u};
+        if (t + WAVES4 < nitems) load_ids(t + WAVES4, nxt);
+        V4_T1(0);
+
+        // ---- G1: A^T = Hot^T · W1^T  (7 n-tiles x 7 k-steps, 49 MFMA) -----
+        // 7 independent accumulator chains, k ascending; the hot fragment
+        // of a k-step is shared by the 7 tiles
+        bf16x8 av[7];  // G2 A-operand fragments a[f = 16mt + lcol][c]
+        {
+            f32x4 acc[7];
+#pragma unroll
+            for (int mt = 0; mt < 7; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kb = 0; kb < 7; ++kb) {
+                const bf16x8 hf =
+                    *reinterpret_cast<const bf16x8*>(hotp + kb * 32);
+#pragma unroll
+                for (int mt = 0; mt < 7; ++mt)
+                    acc[mt] = mfma16x16x32(
+                        hf,
+                        *reinterpret_cast<const bf16x8*>(
+                            w1p + mt * 16 * W1_LD + kb * 32),
+                        acc[mt]);
+            }
+            // un-scatter the hot ones (cheaper than re-zeroing the tile)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (cur[q] < 12) hot[cur[q]][lane + q * 64] = f2bf(0.0f);
+            // lane holds a[f][c = 4lrow + i]; G2 reads a[f][c = 8lrow + j]
+            // with c >= 16 zero: exchange against a zero tile
+#pragma unroll
+            for (int mt = 0; mt < 7; ++mt)
+                av[mt] = c_to_frag(pack_bf16(acc[mt][0], acc[mt][1]),
+                                   pack_bf16(acc[mt][2], acc[mt][3]), 0u, 0u);
+        }
+        V4_T1(1);
+
+        // ---- G2 + G3 per n-tile: t1 = relu(A · E + b1) (7 MFMA), handed to
+        // t2 = relu(W2 · t1 + b2) (4 MFMA) in registers ---------------------
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            unsigned int plo[8], phi[8];
+#pragma unroll
+            for (int mt = 0; mt < 7; ++mt) {
+                const f32x4 acc = mfma16x16x32(av[mt], e_bv[nt],
+                                               f32x4{0.f, 0.f, 0.f, 0.f});
+                plo[mt] = relu_pk(pack_bf16(acc[0] + b1r[mt][0],
+                                            acc[1] + b1r[mt][1]));
+                phi[mt] = relu_pk(pack_bf16(acc[2] + b1r[mt][2],
+                                            acc[3] + b1r[mt][3]));
+            }
+            plo[7] = 0u;  // f = 112..127: k pad of the fourth k-step
+            phi[7] = 0u;
+            bf16x8 tb[4];
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+                tb[kb] = c_to_frag(plo[2 * kb], phi[2 * kb], plo[2 * kb + 1],
+                                   phi[2 * kb + 1]);
+            // v3's two chains: k-steps 0,2 and 1,3
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            acc0 = mfma16x16x32(w2_av[0], tb[0], acc0);
+            acc1 = mfma16x16x32(w2_av[1], tb[1], acc1);
+            acc0 = mfma16x16x32(w2_av[2], tb[2], acc0);
+            acc1 = mfma16x16x32(w2_av[3], tb[3], acc1);
+            // rows j = 4lrow + i (j < 10 live), column e: t2[e * 10 + j]
+            const int e = nt * 16 + lcol;
+            const unsigned int lo = relu_pk(pack_bf16(
+                acc0[0] + acc1[0] + b2r[0], acc0[1] + acc1[1] + b2r[1]));
+            const unsigned int hi = relu_pk(pack_bf16(
+                acc0[2] + acc1[2] + b2r[2], acc0[3] + acc1[3] + b2r[3]));
+            if ((nt < 3 || lcol < E - 48) && lrow < 3) {
+                t2[e * 5 + 2 * lrow] = lo;
+                if (lrow < 2) t2[e * 5 + 2 * lrow + 1] = hi;
+            }
+        }
+        V4_T1(2);
+
+        // ---- coalesced store (wave-wide b128; 8-byte tail on lane 62) -----
+        {
+            bf16* dst = out + ((size_t)w * B + b) * ldo;
+            if (lane * 8 + 8 <= OUT)
+                *reinterpret_cast<u32x4*>(dst + lane * 8) =
+                    *reinterpret_cast<const u32x4*>(&t2[lane * 4]);
+            else if (lane * 8 < OUT)
+                *reinterpret_cast<u32x2*>(dst + lane * 8) =
+                    *reinterpret_cast<const u32x2*>(&t2[lane * 4]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
+        V4_T1(3);
+    }
+    if (timing && tid == 0)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) atomicAdd(&timing[i], tacc[i]);
+#undef V4_T0
+#undef V4_T1
+}
+
+}  // namespace v4
+
+void embed_mlp_fwd4(const uint8_t* ids, const void* w1g, const float* b1,
+                    const void* w2, const float* b2, const void* emb,
+                    void* out, int B, hipStream_t stream,
+                    unsigned long long* timing, int ldo, int max_blocks) {
+    // persistent grid: one workgroup per CU at most (CU count read once)
+    static const int n_cu = [] {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
+                                    dev);
+        return n > 0 ? n : 256;
+    }();
+    int grid = B < n_cu ? B : n_cu;
+    if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+    if (grid < 1) return;
+    hipLaunchKernelGGL(v4::embed_mlp_fwd4_kernel, dim3(grid),
+                       dim3(v4::WAVES4 * 64), 0, stream, ids,
+                       static_cast<const bf16*>(w1g), b1,
+                       static_cast<const bf16*>(w2), b2,
+                       static_cast<const bf16*>(emb), static_cast<bf16*>(out),
+                       B, ldo, timing);
+}
 
 void embed_mlp_fwd3(const uint8_t* ids, const void* w1g, const float* b1,
                     const void* w2, const float* b2, const void* emb,
