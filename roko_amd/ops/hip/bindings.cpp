@@ -30,7 +30,9 @@ void embed_mlp_fwd4(const uint8_t* ids, const void* w1g, const float* b1,
                     unsigned long long* timing, int ldo = 500,
                     int max_blocks = 0);
 void gru_layer_fwd(const void* xg, const void* u, const float* bhh, void* hseq,
-                   void* cache, int T, int B, hipStream_t stream, uint32_t dbg);
+                   void* cache, int T, int B, hipStream_t stream, uint32_t dbg,
+                   int impl = 0);
+int gru_eval_select(int impl, int B);
 void gru_layer_fwd_fused(const void* x, const void* w_ih_p, const void* b_ih,
                          const void* u, const float* bhh, void* xg_ws,
                          void* hseq, int T, int B, int IN, int KP,
@@ -287,7 +289,8 @@ torch::Tensor gru_layer_fused(torch::Tensor x, torch::Tensor w_ih_p,
 //   -> (hseq (T, B, 2, 128) bf16 [, cache (T, B, 2, 512) bf16 when train])
 std::vector<torch::Tensor> gru_layer_fwd(torch::Tensor xg, torch::Tensor u,
                                          torch::Tensor bhh, bool train,
-                                         int64_t dbg) {
+                                         int64_t dbg, int64_t impl,
+                                         c10::optional<torch::Tensor> out_buf) {
     check(xg, torch::kBFloat16, "xg");
     check(u, torch::kBFloat16, "u");
     check(bhh, torch::kFloat32, "bhh");
@@ -296,8 +299,23 @@ std::vector<torch::Tensor> gru_layer_fwd(torch::Tensor xg, torch::Tensor u,
     TORCH_CHECK(u.size(0) == 2 && u.size(1) == 384 && u.size(2) == 128,
                 "u must be (2,384,128)");
     TORCH_CHECK(bhh.size(0) == 2 && bhh.size(1) == 384, "bhh must be (2,384)");
-    TORCH_CHECK(B % 32 == 0, "batch must be a multiple of 32 (pad on host)");
-    auto hseq = torch::empty({T, B, 2, 128}, xg.options());
+    // the 16-row eval tile takes any multiple of 16; training keeps 32
+    TORCH_CHECK(B % 32 == 0 || (!train && B % 16 == 0),
+                "batch must be a multiple of 32 (eval: 16; pad on host)");
+    TORCH_CHECK(T >= 1, "xg must hold at least one step");
+    TORCH_CHECK(impl >= 0 && impl <= 4, "impl: 0 default, 1 old, 2 new; 3 new "
+                "with the other hseq store, 4 new with xg staged through LDS");
+    TORCH_CHECK(impl < 2 || !train, "impl 2..4 are eval kernels");
+    torch::Tensor hseq;
+    if (out_buf.has_value()) {  // caller-owned output (tests prefill it)
+        hseq = *out_buf;
+        check(hseq, torch::kBFloat16, "out");
+        TORCH_CHECK(hseq.dim() == 4 && hseq.size(0) == T && hseq.size(1) == B &&
+                        hseq.size(2) == 2 && hseq.size(3) == 128,
+                    "out must be (T,B,2,128)");
+    } else {
+        hseq = torch::empty({T, B, 2, 128}, xg.options());
+    }
     torch::Tensor cache;
     void* cp = nullptr;
     if (train) {
@@ -305,7 +323,8 @@ std::vector<torch::Tensor> gru_layer_fwd(torch::Tensor xg, torch::Tensor u,
         cp = cache.data_ptr();
     }
     rk::gru_layer_fwd(xg.data_ptr(), u.data_ptr(), bhh.data_ptr<float>(),
-                      hseq.data_ptr(), cp, T, B, cur_stream(), (uint32_t)dbg);
+                      hseq.data_ptr(), cp, T, B, cur_stream(), (uint32_t)dbg,
+                      (int)impl);
     std::vector<torch::Tensor> out{hseq};
     if (train) out.push_back(cache);
     return out;
@@ -1375,7 +1394,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("emb"),
           py::arg("dbg") = 0, py::arg("timing") = c10::nullopt);
     m.def("gru_layer_fwd", &gru_layer_fwd, py::arg("xg"), py::arg("u"),
-          py::arg("bhh"), py::arg("train") = false, py::arg("dbg") = 0);
+          py::arg("bhh"), py::arg("train") = false, py::arg("dbg") = 0,
+          py::arg("impl") = 0, py::arg("out") = c10::nullopt);
+    m.def("gru_eval_impl",
+          [](int64_t B, int64_t impl) {
+              return rk::gru_eval_select((int)impl, (int)B);
+          },
+          py::arg("B"), py::arg("impl") = 0,
+          "which eval GRU kernel gru_layer_fwd(train=False, impl=impl) "
+          "launches at batch B: 1 old, 2 transposed, 3 transposed with the "
+          "other hseq store, 4 transposed with xg staged through LDS");
     m.def("gru_layer_fused", &gru_layer_fused, py::arg("x"), py::arg("w_ih_p"),
           py::arg("b_ih"), py::arg("u"), py::arg("bhh"));
     m.def("gru_layer_bwd", &gru_layer_bwd, py::arg("cache"), py::arg("hseq"),

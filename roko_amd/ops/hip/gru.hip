@@ -22,10 +22,19 @@
 //   * the hidden-state mirror is double-buffered in LDS, so each step needs
 //     exactly ONE __syncthreads(): MFMAs read h[cur] while gate math writes
 //     h[cur^1]; the barrier publishes h[cur^1] for the next step;
-//   * per-step xg tiles (32x384 bf16) are double-buffered through LDS with a
-//     prefetch distance of TWO steps (issue-early / write-late, T14): the
-//     loads for step t+2 issue before anything waits on step t+1's, hiding
-//     the full HBM/L3 latency under one whole step of compute.
+//   * per-step xg tiles (32x384 or 16x384 bf16) are double-buffered through
+//     LDS; the source issues the loads for step t+2 at the top of step t and
+//     writes them to LDS a step later (issue-early / write-late, T14). That
+//     is the intent, not what runs: the loads sit behind runtime branches
+//     (`ti + 2 < T`, the dbg probes), so the compiler must drain them where
+//     it stands — the emitted step loop waits vmcnt(0), or vmcnt(2/1/0),
+//     a few instructions after issuing them, and one xg load latency is
+//     exposed in every step (docs/KERNELS.md lesson 23);
+//   * eval (cache == nullptr, B % 16 == 0) runs gru_eval2_kernel below
+//     instead: operands swapped so a lane's gate inputs are contiguous in
+//     xg and go straight to registers, with a prefetch whose counted waits
+//     were read from the ISA. gru_layer_fwd_kernel<false, 0, 16> stays as
+//     its byte-exact reference (ROKO_GRU_EVAL=v1, or impl=1).
 //
 // PyTorch GRU semantics (gate order r,z,n in weight rows; n-gate bias split):
 //   r = sigmoid(xr + U_r h + bhh_r)
@@ -35,6 +44,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <stdexcept>
 #include <string>
 #include <type_traits>
 
@@ -409,11 +419,376 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gru_layer_fwd_kernel(
     if (ti < T) body(ti, 0, stageA, stageB);
 }
 
+// ---------------------------------------------------------------------------
+// Eval GRU, transposed step (docs/KERNELS.md lesson 23). Same grid, tile,
+// waves, U-in-registers, double-buffered h mirror and one barrier per step as
+// gru_layer_fwd_kernel<false, 0, 16>, and the same arithmetic per output (kb
+// ascending over the same four MFMAs, (x + acc) + bhh, the same sigmoid /
+// tanh / blend expressions, one bf16 round): hseq is byte-identical.
+//
+// The MFMA operands are swapped: the U fragment is A, the h fragment read
+// from the mirror is B (the two fragment layouts are the same, so neither
+// address changes). A lane's accumulator is then
+//     gate[j = j0 + 4*lrow + i][row = lcol],  i = 0..3
+// — four consecutive hidden columns of ONE batch row. So
+//   * a lane's gate inputs are 8 contiguous bytes of the row-major xg per
+//     gate: three global_load_dwordx2 per step straight into registers. No
+//     xg tile in LDS, no staging writes, no 16-bit reads;
+//   * the new h goes to the mirror as one 8-byte write of four packed bf16;
+//   * bhh is four values per gate per lane.
+//
+// Prefetch: the loads for step t + NSET - 1 issue at the top of step t,
+// before the MFMAs, into one of NSET register sets (the loop is unrolled by
+// NSET, so the set is a compile-time choice); the gate phase of the step
+// that consumes them is the first instruction to touch them. No branch
+// surrounds a load — the step index is clamped to T - 1 instead (a re-read of
+// a valid step of this workgroup's rows; no address outside steps [0, T) is
+// formed). sched_barrier(0) after the issue and before the gate phase keeps
+// the scheduler from sinking the loads or hoisting the conversions, so the
+// compiler's own wait is a counted vmcnt(N) that only covers loads a full
+// step old.
+//
+// h mirror pitch audit (HPAD = 136 bf16 = 272 B = 68 dwords, unchanged):
+//   * fragment reads, ds_read_b128, four 16-lane groups, bank = dword mod
+//     64: lane (lrow, lcol) reads 16-B slot (17*lcol + lrow + 4*kb) mod 16 =
+//     (lcol + lrow) mod 16. Group {0-3, 12-15, 20-27} holds lrow 0 with lcol
+//     0-3, 12-15 (slots 0-3, 12-15) and lrow 1 with lcol 4-11 (slots 5-12):
+//     slot 12 twice, every other slot at most once — one 2-way conflict, 5
+//     LDS cycles where 4 is the floor; the other three groups are the same
+//     picture shifted. These are the reads the old kernel does too.
+//   * mirror writes, ds_write_b64, four contiguous 16-lane groups (one lrow,
+//     lcol 0-15), bank = dword mod 32: dword = 68*lcol + 8*wid + 2*lrow, so
+//     lcol and lcol + 8 share a bank pair: 2-way, 8 array cycles against the
+//     instruction's own 6. Any 16-B-aligned pitch is a multiple of 4 dwords
+//     and gives >= 2-way here; 2-way is the best a row-per-lane 8-byte write
+//     can do without a swizzle.
+//   * a 288-B pitch would make the reads conflict-free (slot 2*lcol + lrow)
+//     and the writes 4-way: -16 and +8 LDS cycles per wave per step, a net
+//     ~64 cycles per workgroup per ~1,900-cycle step on a pipe that is idle
+//     most of the step. HPAD stays.
+//
+// DBG (compile time, timing probes only; production is DBG = 0):
+//   1 no hseq store, 4 no gate VALU, 8 no xg loads, 16 no MFMA.
+// HSREG: hseq is stored from the packed registers before the barrier (true)
+// or from the mirror after it, coalesced (false).
+// STAGED: the fallback form, kept for the timing script — coalesced 8-byte
+// loads of the whole 16 x 384 step tile, parked in LDS a step later behind
+// the same counted waits, read back with three ds_read_b64 per lane.
+// Resources of the shipped <0, 2, false, false>: 108 VGPRs, 0 AGPRs, 0
+// scratch, 8,704 B LDS (old kernel: 118 / 0 / 0 / 33,280 B).
+using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+
+constexpr int E2_MBT = 16;
+constexpr int E2_NSET = 2;        // shipped: prefetch distance one step
+constexpr bool E2_HSREG = false;  // shipped hseq store
+// STAGED tile pitch: 392 bf16 = 196 dwords. The three ds_read_b64 per lane
+// (two 32-lane groups, bank = dword mod 64) touch dwords 196*lcol + 8*wid +
+// 2*lrow + {0, 1} = 4*lcol + 2*lrow + c (mod 64): 64 distinct banks per
+// group. The unpadded 384 puts all 16 rows of a group on the same banks.
+constexpr int E2_XPAD = G3 + 8;
+
+RK_DEV float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
+RK_DEV float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+RK_DEV uint32_t pack_bf16x2(float a, float b) {
+    union {
+        bf16x2 v;
+        uint32_t w;
+    } p;
+    p.v = __builtin_convertvector(f32x2{a, b}, bf16x2);
+    return p.w;
+}
+
+template <int DBG, int NSET, bool HSREG, bool STAGED = false>
+__global__ __launch_bounds__(WAVES * 64, 2) void gru_eval2_kernel(
+    const bf16* __restrict__ xg,   // (T, B, 2, 3H)  W_ih·x + b_ih
+    const bf16* __restrict__ u,    // (2, 3H, H)     weight_hh
+    const float* __restrict__ bhh, // (2, 3H)        bias_hh
+    bf16* __restrict__ hseq,       // (T, B, 2, H)   output
+    int T, int B) {
+    static_assert(!STAGED || NSET == 2, "the staged form has two sets");
+    constexpr int DIST = NSET - 1;  // register sets loaded ahead of the loop
+    // step distance of the load a step issues: the staged form parks a set
+    // in LDS one step before its use, so it looks one step further
+    constexpr int LOOK = STAGED ? NSET : NSET - 1;
+    constexpr int HBUF = E2_MBT * HPAD;
+    constexpr int XBUF = E2_MBT * E2_XPAD;
+    __shared__ bf16 hm[2 * HBUF];   // double-buffered hidden-state mirror
+    __shared__ bf16 xst[STAGED ? 2 * XBUF : 1];  // STAGED: xg step tiles
+
+    const int dir = blockIdx.y;
+    const int b0 = blockIdx.x * E2_MBT;
+    const int tid = threadIdx.x;
+    const int wid = tid >> 6;
+    const int lane = tid & 63;
+    const int lrow = lane >> 4;
+    const int lcol = lane & 15;
+    const int j0 = wid * 16;          // this wave's 16 hidden columns
+    const int jl = j0 + 4 * lrow;     // this lane's four hidden columns
+    if (wid >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
+
+    // A-fragment: A[m = lcol][k] = U[g*H + j0 + lcol][kb*32 + 8*lrow + ..]
+    bf16x8 ufrag[3][4];
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb)
+            ufrag[g][kb] = *reinterpret_cast<const bf16x8*>(
+                u + (size_t)dir * G3 * H + (size_t)(g * H + j0 + lcol) * H +
+                kb * 32 + 8 * lrow);
+    float bhh_reg[3][4];
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            bhh_reg[g][i] = bhh[dir * G3 + g * H + jl + i];
+
+    float hreg[4] = {0.f, 0.f, 0.f, 0.f};  // fp32 master copy of h
+    for (int e = tid; e < HBUF; e += WAVES * 64) hm[e] = f2bf(0.0f);
+
+    const int stp = (dir == 0) ? 1 : -1;
+    const int tfirst = (dir == 0) ? 0 : T - 1;
+    const size_t xstep = (size_t)B * 2 * G3;
+    const bf16* xlane = xg + ((size_t)(b0 + lcol) * 2 + dir) * G3 + jl;
+    // STAGED: chunk c = 512*p + tid of the 16 x 384 step tile, 4 bf16 each
+    // (96 chunks per row: a 16-lane group never straddles a row)
+    int srow[3], scol[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        const int e = (p * WAVES * 64 + tid) * 4;
+        srow[p] = e / G3;
+        scol[p] = e % G3;
+    }
+    // xg of step index s (clamped into [0, T)) -> one register set
+    auto load_x = [&](int s, u32x2 (&set)[3]) {
+        const int sc = s < T - 1 ? s : T - 1;
+        const size_t toff = (size_t)(tfirst + stp * sc) * xstep;
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            if constexpr (STAGED)
+                set[g] = *reinterpret_cast<const u32x2*>(
+                    xg + toff + ((size_t)(b0 + srow[g]) * 2 + dir) * G3 +
+                    scol[g]);
+            else
+                set[g] =
+                    *reinterpret_cast<const u32x2*>(xlane + toff + g * H);
+        }
+    };
+    auto stage_x = [&](int buf_off, const u32x2 (&set)[3]) {
+#pragma unroll
+        for (int g = 0; g < 3; ++g)
+            *reinterpret_cast<u32x2*>(xst + buf_off + srow[g] * E2_XPAD +
+                                      scol[g]) = set[g];
+    };
+
+    u32x2 xs[NSET][3];
+#pragma unroll
+    for (int s = 0; s < NSET; ++s)
+#pragma unroll
+        for (int g = 0; g < 3; ++g) xs[s][g] = u32x2{0u, 0u};
+    if constexpr (STAGED && !(DBG & 8)) {
+        load_x(0, xs[1]);
+        stage_x(0, xs[1]);  // step 0 straight into tile buffer 0
+        load_x(1, xs[0]);
+    } else if constexpr (!(DBG & 8)) {
+#pragma unroll
+        for (int s = 0; s < DIST; ++s) load_x(s, xs[s]);
+    }
+    // Drain the prologue (U, bhh and the first xg sets, all needed by step
+    // 0 anyway) so the loop is entered with nothing in flight. Entered with
+    // loads pending, the compiler's counted waits inside the loop must also
+    // be right for the entry path, and come out as vmcnt(5/4/3) where the
+    // steady state allows 7/6/5: each step would wait for the hseq store
+    // issued just before it.
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
+    __syncthreads();
+
+    int rd = 0;   // element offset of the mirror buffer this step reads
+    int xrd = 0;  // STAGED: element offset of the xg tile this step reads
+    auto body = [&](int ti, u32x2 (&x_ld)[3], u32x2 (&x)[3]) {
+        const int t = tfirst + stp * ti;
+        const int wr = rd ^ HBUF;
+        if constexpr (!(DBG & 8)) load_x(ti + LOOK, x_ld);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (STAGED && !(DBG & 8)) {
+            // park the set loaded a step ago (step ti + 1) in the back tile
+#pragma unroll
+            for (int g = 0; g < 3; ++g) asm volatile("" : "+v"(x[g]));
+            stage_x(xrd ^ XBUF, x);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+
+        // gates_h^T = U · h^T  (12 MFMA per wave, h fragment shared 3-ways)
+        f32x4 acc[3];
+        if constexpr (DBG & 16) {
+#pragma unroll
+            for (int g = 0; g < 3; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) {
+                const bf16x8 hf = lds_load_a_frag(hm + rd, 0, kb * 32, HPAD);
+#pragma unroll
+                for (int g = 0; g < 3; ++g)
+                    acc[g] = mfma16x16x32(
+                        ufrag[g][kb], hf,
+                        kb == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[g]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // the set is opaque up to here: without this the bf16 -> f32 shifts
+        // of x are placed above the MFMAs and take the vmcnt wait with them
+        u32x2 xv[3];
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            if constexpr (STAGED) {
+                xv[g] = *reinterpret_cast<const u32x2*>(
+                    xst + xrd + lcol * E2_XPAD + g * H + jl);
+            } else {
+                asm volatile("" : "+v"(x[g]));
+                xv[g] = x[g];
+            }
+        }
+
+        float hnew[4];
+        if constexpr (DBG & 4) {  // timing: gate math stripped, loads kept
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                hnew[i] = acc[0][i] + acc[1][i] + acc[2][i];
+        } else {
+            float xr[4], xz[4], xn[4];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                xr[2 * p] = bf_lo(xv[0][p]);
+                xr[2 * p + 1] = bf_hi(xv[0][p]);
+                xz[2 * p] = bf_lo(xv[1][p]);
+                xz[2 * p + 1] = bf_hi(xv[1][p]);
+                xn[2 * p] = bf_lo(xv[2][p]);
+                xn[2 * p + 1] = bf_hi(xv[2][p]);
+            }
+            float r4[4], z4[4], n4[4], hg4[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                hg4[i] = acc[2][i] + bhh_reg[2][i];
+                r4[i] = sigmoidf_dev(xr[i] + acc[0][i] + bhh_reg[0][i]);
+                z4[i] = sigmoidf_dev(xz[i] + acc[1][i] + bhh_reg[1][i]);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                n4[i] = tanhf_dev(xn[i] + r4[i] * hg4[i]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                hnew[i] = (1.0f - z4[i]) * n4[i] + z4[i] * hreg[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hreg[i] = hnew[i];
+        const u32x2 pk = {pack_bf16x2(hnew[0], hnew[1]),
+                          pack_bf16x2(hnew[2], hnew[3])};
+        *reinterpret_cast<u32x2*>(hm + wr + lcol * HPAD + jl) = pk;
+        bf16* dst = hseq + (((size_t)t * B + b0) * 2 + dir) * H;
+        if constexpr (HSREG && !(DBG & 1))
+            *reinterpret_cast<u32x2*>(dst + (size_t)lcol * 2 * H + jl) = pk;
+        __syncthreads();  // h[wr] published
+        if constexpr (!HSREG && !(DBG & 1)) {
+            // cooperative store from the mirror: 8 B per lane, a wave
+            // covers two whole 256-B rows
+            const int row = tid >> 5, col = (tid & 31) * 4;
+            *reinterpret_cast<u32x2*>(dst + (size_t)row * 2 * H + col) =
+                *reinterpret_cast<const u32x2*>(hm + wr + row * HPAD + col);
+        }
+        rd = wr;
+        if constexpr (STAGED) xrd ^= XBUF;
+    };
+
+    int ti = 0;
+    for (; ti + NSET <= T; ti += NSET) {
+#pragma unroll
+        for (int s = 0; s < NSET; ++s)
+            body(ti + s, xs[(s + DIST) % NSET], xs[s]);
+    }
+#pragma unroll
+    for (int s = 0; s < NSET - 1; ++s)
+        if (ti + s < T) body(ti + s, xs[(s + DIST) % NSET], xs[s]);
+}
+
+static void launch_eval2(const bf16* xg, const bf16* u, const float* bhh,
+                         bf16* hseq, int T, int B, hipStream_t stream,
+                         uint32_t dbg) {
+    const dim3 grid(B / E2_MBT, 2), block(WAVES * 64);
+#define RK_E2(D)                                                             \
+    hipLaunchKernelGGL((gru_eval2_kernel<D, E2_NSET, E2_HSREG>), grid,       \
+                       block, 0, stream, xg, u, bhh, hseq, T, B)
+    switch (dbg) {
+        case 0: RK_E2(0); break;
+        case 1: RK_E2(1); break;
+        case 4: RK_E2(4); break;
+        case 8: RK_E2(8); break;
+        case 16: RK_E2(16); break;
+        default:
+            throw std::invalid_argument(
+                "gru eval2 probe mask must be one of 0, 1, 4, 8, 16");
+    }
+#undef RK_E2
+}
+
+// Which eval kernel a gru_layer_fwd(cache == nullptr) call launches:
+// 1 the old kernels, 2 the transposed kernel; for the timing script only, 3
+// the transposed kernel with the hseq store variant that is not shipped and
+// 4 the transposed kernel with xg staged through LDS (the fallback form).
+// impl: 0 default (the transposed kernel; ROKO_GRU_EVAL=v1 or ROKO_GRU_MB=32
+// make that the old kernels, process-wide), 1/2/3 as above.
+int gru_eval_select(int impl, int B) {
+    static const bool eval_v1 = [] {
+        const char* f = getenv("ROKO_GRU_EVAL");
+        return f && std::string(f) == "v1";
+    }();
+    static const bool mb32 = [] {
+        const char* f = getenv("ROKO_GRU_MB");
+        return f && std::string(f) == "32";
+    }();
+    if (impl < 0 || impl > 4)
+        throw std::invalid_argument("gru_layer_fwd: impl must be 0..4");
+    if (impl >= 2 && (B % 16) != 0)
+        throw std::invalid_argument(
+            "the transposed eval GRU needs a batch that is a multiple of 16");
+    if (impl >= 2) return impl;
+    return (impl == 0 && !eval_v1 && !mb32 && (B % 16) == 0) ? 2 : 1;
+}
+
 void gru_layer_fwd(const void* xg, const void* u, const float* bhh, void* hseq,
                    void* cache, int T, int B, hipStream_t stream,
-                   uint32_t dbg) {
+                   uint32_t dbg, int impl) {
     dim3 grid(B / MB, 2);
     dim3 block(WAVES * 64);
+    if (cache && impl >= 2)
+        throw std::invalid_argument("impl 2..4 are eval kernels");
+    const int sel = cache ? 1 : gru_eval_select(impl, B);
+    if (sel >= 2) {
+        if (sel >= 3) {
+            if (dbg)
+                throw std::invalid_argument(
+                    "probe masks exist for the shipped eval kernel only");
+            if (sel == 3)
+                hipLaunchKernelGGL(
+                    (gru_eval2_kernel<0, E2_NSET, !E2_HSREG>),
+                    dim3(B / E2_MBT, 2), block, 0, stream,
+                    static_cast<const bf16*>(xg),
+                    static_cast<const bf16*>(u), bhh,
+                    static_cast<bf16*>(hseq), T, B);
+            else
+                hipLaunchKernelGGL(
+                    (gru_eval2_kernel<0, 2, E2_HSREG, true>),
+                    dim3(B / E2_MBT, 2), block, 0, stream,
+                    static_cast<const bf16*>(xg),
+                    static_cast<const bf16*>(u), bhh,
+                    static_cast<bf16*>(hseq), T, B);
+        } else {
+            launch_eval2(static_cast<const bf16*>(xg),
+                         static_cast<const bf16*>(u), bhh,
+                         static_cast<bf16*>(hseq), T, B, stream, dbg);
+        }
+        return;
+    }
     // MBT=16 halves each thread's gate-chain count — the gate phase sits
     // at the 2-wave VALU-issue floor, so the wall nearly halves (eval
     // 175.6 -> 97.7 us measured) and the WG count doubles (serving
@@ -446,7 +821,8 @@ void gru_layer_fwd(const void* xg, const void* u, const float* bhh, void* hseq,
             const char* f = getenv("ROKO_GRU_MB");
             return (f && std::string(f) == "32") ? 32 : 16;
         }();
-        if (mb_eval == 16 && (B % 16) == 0)
+        // (a batch that is a multiple of 16 only has no 32-row form)
+        if ((mb_eval == 16 || (B % 32) != 0) && (B % 16) == 0)
             hipLaunchKernelGGL((gru_layer_fwd_kernel<false, 0, 16>),
                                dim3(B / 16, 2), block, 0, stream,
                                static_cast<const bf16*>(xg),

@@ -9,13 +9,15 @@ xg = (torch.randn(T, B, 2, 384, device="cuda") * 0.3).to(torch.bfloat16)
 u = (torch.randn(2, 384, 128, device="cuda") * 0.2).to(torch.bfloat16)
 bhh = torch.randn(2, 384, device="cuda")
 
+# impl=1: the runtime probe masks (and their combinations) belong to the
+# LDS-staged kernels; scripts/gru_eval2_timing.py probes the eval default
 def run(train, dbg, label, iters=30):
     for _ in range(3):
-        ext.gru_layer_fwd(xg, u, bhh, train, dbg)
+        ext.gru_layer_fwd(xg, u, bhh, train, dbg, impl=1)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(iters):
-        ext.gru_layer_fwd(xg, u, bhh, train, dbg)
+        ext.gru_layer_fwd(xg, u, bhh, train, dbg, impl=1)
     torch.cuda.synchronize()
     us = (time.perf_counter() - t0) / iters * 1e6
     print(f"{label:38s} {us:8.1f} us  ({us/T*1000:6.0f} ns/step)")
