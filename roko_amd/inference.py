@@ -30,7 +30,7 @@ from torch.utils.data import DataLoader
 
 from . import config as C
 from .datasets import InferenceDataset
-from .io.fasta import write_fasta
+from .io.fasta import write_fasta, write_fastq
 from .model import RokoModel
 from .parallel.ddp import init_distributed
 from .rkdata import RkwFile
@@ -181,17 +181,20 @@ def stitch_dense(draft: str, maj: np.ndarray) -> str:
     return draft[:first] + mid + draft[last + 1:]
 
 
-def _infer_device_votes(rkw, dl, model, batch_size, depth, meter):
+def _infer_device_votes(rkw, dl, model, batch_size, depth, meter,
+                        quality=False):
     """RKW windows -> DeviceVotes: predictions and vote tables stay on the
-    GPU; returns ({contig: polished}, windows). Positions are fetched per
-    batch from the mmap in runs of one window group."""
+    GPU; returns ({contig: polished}, windows, {contig: quality string} or
+    None). Positions are fetched per batch from the mmap in runs of one
+    window group."""
     from .ops.forward import InferencePipeline
     from .ops.votes import DeviceVotes
 
     lens = {c["name"]: int(c["len"]) for c in rkw.meta["contigs"]}
     # votes mode runs one batch per slot (coalesce=1)
-    pipe = InferencePipeline(model, batch_size, depth=depth, coalesce=1)
-    dv = DeviceVotes(lens, pipe)
+    pipe = InferencePipeline(model, batch_size, depth=depth, coalesce=1,
+                             quality=quality)
+    dv = DeviceVotes(lens, pipe, quality=quality)
     group_contig = [g["contig"] for g in rkw.groups]
     n_windows = 0
     for gis, js, x in dl:
@@ -220,14 +223,39 @@ def _infer_device_votes(rkw, dl, model, batch_size, depth, meter):
         n_windows += len(gis)
         meter.add(windows=len(gis), bases=len(gis) * C.WINDOW_STRIDE)
     out: Dict[str, str] = {}
+    quals: Optional[Dict[str, str]] = {} if quality else None
     for name in rkw.contig_names():
         draft = rkw.contig_seq(name)
-        if dv.has_votes(name):
-            out[name] = stitch_dense(draft, dv.consensus(name))
+        if not dv.has_votes(name):
+            out[name] = draft
+        elif quality:
+            from .quality import stitch_dense_qual
+
+            out[name], quals[name] = stitch_dense_qual(
+                draft, *dv.consensus_quality(name))
             dv.free(name)
         else:
-            out[name] = draft
-    return out, n_windows
+            out[name] = stitch_dense(draft, dv.consensus(name))
+            dv.free(name)
+    return out, n_windows, quals
+
+
+def _write_outputs(out: Dict[str, str], quals: Optional[Dict[str, str]],
+                   out_path: Optional[str], out_fastq: Optional[str],
+                   log) -> None:
+    """FASTA and/or FASTQ of the polished contigs, sorted by name. A contig
+    without an entry in `quals` came through as draft: all Q0."""
+    if out_path:
+        write_fasta(out_path, sorted(out.items()))
+        log(f"wrote {len(out)} polished contigs to {out_path}")
+    if out_fastq:
+        from .quality import unpolished_quality
+
+        write_fastq(out_fastq,
+                    [(name, seq, quals.get(name) or unpolished_quality(seq))
+                     for name, seq in sorted(out.items())])
+        log(f"wrote {len(out)} polished contigs with qualities to "
+            f"{out_fastq}")
 
 
 def infer(
@@ -239,8 +267,9 @@ def infer(
     device: Optional[torch.device] = None,
     model: Optional[RokoModel] = None,
     log=print,
-    votes: str = "host",
+    votes: Optional[str] = None,
     depth: int = 48,
+    out_fastq: Optional[str] = None,
 ) -> Dict[str, str]:
     """Polish the draft in `data_path` (RKW inference file) and return
     {contig: polished sequence}. Writes FASTA if `out_path` is given.
@@ -251,11 +280,20 @@ def infer(
 
     votes="device" keeps predictions and vote tables on the GPU
     (ops/votes.py); single process, GPU only. `depth` is the number of
-    in-flight batches of the GPU pipeline.
+    in-flight batches of the GPU pipeline. `votes` left at None means
+    "host", except that `out_fastq` on a GPU selects "device".
+
+    `out_fastq` also writes a FASTQ with a Phred quality per polished base
+    (roko_amd/quality.py). Single process only. On a GPU the qualities are
+    computed on the device and need votes="device"; on the CPU the host
+    route computes them.
     """
-    if votes not in ("host", "device"):
+    if votes not in (None, "host", "device"):
         raise ValueError(f"votes must be 'host' or 'device', got {votes!r}")
     rank, local_rank, world = init_distributed()
+    if out_fastq and world > 1:
+        raise ValueError("out_fastq is single-process only "
+                         f"(WORLD_SIZE={world}); run one process")
     if votes == "device" and world > 1:
         raise ValueError("votes='device' is single-process only "
                          f"(WORLD_SIZE={world}); use votes='host'")
@@ -265,6 +303,16 @@ def infer(
             if torch.cuda.is_available()
             else torch.device("cpu")
         )
+    device = torch.device(device)
+    if out_fastq and device.type == "cuda":
+        if votes == "host":
+            raise ValueError(
+                "out_fastq on a GPU computes the qualities on the device "
+                "and needs votes='device' (or leave votes unset)")
+        votes = "device"
+    if votes is None:
+        votes = "host"
+    quality = bool(out_fastq)
 
     if model is None:
         model = RokoModel()
@@ -281,26 +329,36 @@ def infer(
                     pin_memory=torch.cuda.is_available())
 
     # streaming per-contig vote accumulation (bounded memory)
-    sv = StreamingVotes()
+    if quality:
+        from .quality import StreamingQualityVotes, phred_units, stitch_tables
 
-    def account(gis, js, preds):
+        sv = StreamingQualityVotes()
+    else:
+        sv = StreamingVotes()
+
+    def account(gis, js, preds, units=None):
         for k in range(len(gis)):
             g, pos_arr, _, _ = rkw.group_arrays(int(gis[k]))
-            sv.add(g["contig"], np.asarray(pos_arr[js[k]]), preds[k])
+            if units is None:
+                sv.add(g["contig"], np.asarray(pos_arr[js[k]]), preds[k])
+            else:
+                sv.add(g["contig"], np.asarray(pos_arr[js[k]]), preds[k],
+                       units[k])
 
     t0 = time.time()
     n_windows = 0
     meter = Meter("inference", rank=rank)
     pipe = None
     out: Optional[Dict[str, str]] = None
+    quals: Optional[Dict[str, str]] = None
     if device.type == "cuda" and votes == "host":
         from .ops.forward import InferencePipeline
 
         pipe = InferencePipeline(model, batch_size, depth=depth)
     with torch.no_grad():
         if votes == "device":
-            out, n_windows = _infer_device_votes(rkw, dl, model, batch_size,
-                                                 depth, meter)
+            out, n_windows, quals = _infer_device_votes(
+                rkw, dl, model, batch_size, depth, meter, quality)
         elif pipe is not None:
             # pipelined: keep `depth` batches in flight; votes are harvested
             # one pipeline-depth behind submission
@@ -323,7 +381,9 @@ def infer(
                 preds = logits.argmax(dim=2).to(torch.uint8).cpu().numpy()
                 n_windows += len(gis)
                 meter.add(windows=len(gis), bases=len(gis) * C.WINDOW_STRIDE)
-                account(gis.numpy(), js.numpy(), preds)
+                account(gis.numpy(), js.numpy(), preds,
+                        phred_units(logits.cpu().numpy()) if quality
+                        else None)
     meter.close()
     dt = time.time() - t0
     bases = n_windows * C.WINDOW_STRIDE
@@ -333,12 +393,13 @@ def infer(
     )
 
     if out is not None:
-        if out_path:
-            write_fasta(out_path, sorted(out.items()))
-            log(f"wrote {len(out)} polished contigs to {out_path}")
+        _write_outputs(out, quals, out_path, out_fastq, log)
         return out
 
-    tables: VoteTable = sv.finalize()
+    if quality:
+        tables, sums = sv.finalize()
+    else:
+        tables: VoteTable = sv.finalize()
 
     if world > 1:
         gathered: List[Optional[VoteTable]] = [None] * world if rank == 0 else None
@@ -354,15 +415,21 @@ def infer(
         tables = merged
 
     out = {}
+    quals = {}
     for name in rkw.contig_names():
         draft = rkw.contig_seq(name)
         if name in tables:
             out[name] = stitch_contig(draft, *tables[name])
+            if quality:
+                seq, quals[name] = stitch_tables(draft, tables[name],
+                                                 sums[name])
+                if seq != out[name]:
+                    raise RuntimeError(
+                        f"{name}: the quality stitch disagrees with the "
+                        "sequence stitch")
         else:
             out[name] = draft
-    if out_path:
-        write_fasta(out_path, sorted(out.items()))
-        log(f"wrote {len(out)} polished contigs to {out_path}")
+    _write_outputs(out, quals, out_path, out_fastq, log)
     return out
 
 
@@ -373,8 +440,13 @@ def main(argv=None):
     p.add_argument("out", help="output FASTA path")
     p.add_argument("--t", type=int, default=0, help="DataLoader workers")
     p.add_argument("--b", type=int, default=C.BATCH_SIZE, help="batch size")
+    p.add_argument("--fastq", default=None, metavar="PATH",
+                   help="also write FASTQ with a Phred quality per polished "
+                        "base (single process; on a GPU the votes run on "
+                        "the device)")
     a = p.parse_args(argv)
-    infer(a.data, a.model, a.out, batch_size=a.b, workers=a.t)
+    infer(a.data, a.model, a.out, batch_size=a.b, workers=a.t,
+          out_fastq=a.fastq)
 
 
 if __name__ == "__main__":

@@ -51,3 +51,37 @@ def write_fasta(path: str, records, width: int = 80) -> None:
             for i in range(0, len(seq), width):
                 fh.write(seq[i : i + width])
                 fh.write("\n")
+
+
+def write_fastq(path: str, records) -> None:
+    """Write ``(name, sequence, quality)`` triples as 4-line FASTQ records,
+    unwrapped; `quality` is the Phred+33 string, one char per base. Creates
+    parent dirs."""
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    with open(path, "w") as fh:
+        for name, seq, qual in records:
+            if len(seq) != len(qual):
+                raise ValueError(
+                    f"{name}: {len(seq)} bases but {len(qual)} qualities")
+            fh.write(f"@{name}\n{seq}\n+\n{qual}\n")
+
+
+def read_fastq(path: str) -> Iterator[Tuple[str, str, str]]:
+    """Yield ``(name, sequence, quality)`` per 4-line record (the form
+    `write_fastq` writes). Name = header up to first space."""
+    with _open_text(path) as fh:
+        while True:
+            head = fh.readline()
+            if not head:
+                return
+            head = head.rstrip("\n")
+            if not head:
+                continue
+            seq = fh.readline().rstrip("\n")
+            plus = fh.readline().rstrip("\n")
+            qual = fh.readline().rstrip("\n")
+            if not head.startswith("@") or not plus.startswith("+") \
+                    or len(seq) != len(qual):
+                raise ValueError(f"{path}: malformed FASTQ record {head!r}")
+            yield head[1:].split()[0], seq, qual

@@ -184,7 +184,8 @@ class InferencePipeline:
     """
 
     def __init__(self, model, batch: int, depth: int = 4,
-                 use_graphs: bool = True, coalesce=None):
+                 use_graphs: bool = True, coalesce=None,
+                 quality: bool = False):
         from . import require
 
         require()
@@ -193,12 +194,21 @@ class InferencePipeline:
         self.model = model
         self.w = _bf16_weights(model)
         self.use_graphs = use_graphs
+        # quality=True: the slots' head kernel also writes five quality
+        # units per column (roko_amd/quality.py) for the votes mode; fixed
+        # at construction, and off it leaves the slots exactly as they were
+        self.quality = bool(quality)
         dev = next(model.parameters()).device
         if coalesce is None:
             coalesce = int(os.environ.get("ROKO_COALESCE", _COALESCE_DEFAULT))
         # only the C++ slot can be filled in parts
         cpp_ok = use_graphs and os.environ.get("ROKO_SERVE") != "graph" \
             and hasattr(_ext(), "ServeSlot")
+        if self.quality and not cpp_ok:
+            raise RuntimeError(
+                "quality output needs the C++ serving slot (ext.ServeSlot); "
+                "it is not available with ROKO_SERVE=graph or "
+                "use_graphs=False")
         self.coalesce = coalesce_width(coalesce, depth) if cpp_ok else 1
         self.slots = []
         for _ in range(depth // self.coalesce):
@@ -253,17 +263,18 @@ class InferencePipeline:
         return self.slots[self._next % self.depth].votes_staging()
 
     def submit_votes(self, n: int, table: torch.Tensor, n_slots: int,
-                     err_flag: torch.Tensor) -> None:
+                     err_flag: torch.Tensor, qsum=None) -> None:
         """Enqueue rows 0..n of the current staging: H2D, model, and one vote
-        per column into `table`. No predictions come back."""
+        per column into `table` (and its quality units into `qsum`, on a
+        quality pipeline). No predictions come back."""
         self._need_uncoalesced()
         slot = self.slots[self._next % self.depth]
         self._next += 1
-        slot.submit_votes(n, table, n_slots, err_flag)
+        slot.submit_votes(n, table, n_slots, err_flag, qsum)
 
     def submit_votes_device(self, x: torch.Tensor, pos: torch.Tensor, n: int,
                             table: torch.Tensor, n_slots: int,
-                            err_flag: torch.Tensor) -> None:
+                            err_flag: torch.Tensor, qsum=None) -> None:
         """submit_votes() for windows that are already in device memory
         (ops/windows.py): x (>=n, R, W) u8 and pos (>=n, W, 2) i32 on the
         GPU, n <= batch. The slot copies them device to device on its own
@@ -277,7 +288,7 @@ class InferencePipeline:
             raise ValueError(f"n={n} outside [0, min(batch, rows given)]")
         slot = self.slots[self._next % self.depth]
         self._next += 1
-        slot.submit_votes_device(x, pos, n, table, n_slots, err_flag)
+        slot.submit_votes_device(x, pos, n, table, n_slots, err_flag, qsum)
 
     def _need_uncoalesced(self):
         if self.coalesce != 1:
@@ -353,7 +364,12 @@ class _Slot:
         ext = _ext()
         if pipe.use_graphs and os.environ.get("ROKO_SERVE") != "graph" \
                 and hasattr(ext, "ServeSlot"):
-            self.cpp = ext.ServeSlot(self.pipe.w, batch, self.host_out, parts)
+            if pipe.quality:
+                self.cpp = ext.ServeSlot(self.pipe.w, batch, self.host_out,
+                                         parts, True)
+            else:
+                self.cpp = ext.ServeSlot(self.pipe.w, batch, self.host_out,
+                                         parts)
             # one warm-up pass primes the hipBLASLt workspace/algo cache for
             # the slot stream so submit() never allocates
             warm = torch.zeros((batch, C.WINDOW_ROWS, C.WINDOW_COLS),
@@ -412,14 +428,15 @@ class _Slot:
                 (b, C.WINDOW_COLS, 2), dtype=torch.int32, pin_memory=True)
         return self.x_stage.numpy(), self.pos_stage.numpy()
 
-    def submit_votes(self, n: int, table, n_slots: int, err_flag):
+    def submit_votes(self, n: int, table, n_slots: int, err_flag,
+                     qsum=None):
         if getattr(self, "x_stage", None) is None:
             raise RuntimeError("call votes_staging() and fill it first")
         self.cpp.submit_votes(self.x_stage, self.pos_stage, n, table,
-                              n_slots, err_flag)
+                              n_slots, err_flag, qsum)
 
     def submit_votes_device(self, x, pos, n: int, table, n_slots: int,
-                            err_flag):
+                            err_flag, qsum=None):
         if self.cpp is None:
             raise RuntimeError(
                 "votes mode needs the C++ serving slot (ext.ServeSlot); it is "
@@ -433,7 +450,7 @@ class _Slot:
         # batches (and the window tensors they pin) are in flight
         self.wait_done()
         self.cpp.submit_votes(x.contiguous(), pos.contiguous(), n, table,
-                              n_slots, err_flag)
+                              n_slots, err_flag, qsum)
 
     def submit(self, x: torch.Tensor, copy_out: bool, part: int = 0):
         n = x.shape[0]

@@ -51,7 +51,8 @@ void adam_mt(const int64_t* table, int n_params, float* p, float* m, float* v,
 void grad_gather(const int64_t* table, int n_params, float* flat_g,
                  hipStream_t stream);
 void head_fwd(const void* hseq, const void* w4, const float* b4, float* logits,
-              uint8_t* amax, int T, int B, hipStream_t stream);
+              uint8_t* amax, int T, int B, hipStream_t stream,
+              uint8_t* qv = nullptr);
 void emb_grad(const void* dm, const uint8_t* ids, float* de, int64_t n,
               hipStream_t stream);
 void front_fwd(const uint8_t* ids, const void* w1, const float* b1,
@@ -91,6 +92,13 @@ void vote_scatter(const uint8_t* preds, const int32_t* positions,
                   int n_cols, hipStream_t stream);
 void vote_consensus(const uint32_t* table, int64_t n_slots, uint8_t* maj,
                     hipStream_t stream);
+void vote_scatter_q(const uint8_t* preds, const uint8_t* units,
+                    const int32_t* positions, uint32_t* table, uint64_t* qsum,
+                    int64_t n_slots, uint32_t* err_flag, int n_cols,
+                    hipStream_t stream);
+void vote_consensus_q(const uint32_t* table, const uint64_t* qsum,
+                      int64_t n_slots, uint8_t* maj, uint8_t* qual,
+                      hipStream_t stream);
 bool windows_geometry_ok(int rows, int cols, int stride, int max_ins);
 void windows_index(const int32_t* ref_start, const int32_t* ref_end,
                    const uint8_t* reverse, const uint32_t* cigar_off,
@@ -428,19 +436,22 @@ torch::Tensor emb_grad(torch::Tensor dm, torch::Tensor ids) {
     return de;
 }
 
-// hseq (T, B, 256) bf16 -> (logits (B,T,5) f32, argmax (B,T) u8) per flags
+// hseq (T, B, 256) bf16 -> (logits (B,T,5) f32, argmax (B,T) u8, quality
+// units (B,T,5) u8) per flags, in that order
 std::vector<torch::Tensor> head_fwd(torch::Tensor hseq, torch::Tensor w4,
                                     torch::Tensor b4, bool want_logits,
-                                    bool want_argmax) {
+                                    bool want_argmax,
+                                    bool want_quality = false) {
     check(hseq, torch::kBFloat16, "hseq");
     check(w4, torch::kBFloat16, "w4");
     check(b4, torch::kFloat32, "b4");
     const int T = hseq.size(0), B = hseq.size(1);
     TORCH_CHECK(hseq.size(2) == 256, "hseq must be (T,B,256)");
     TORCH_CHECK(w4.size(0) == 5 && w4.size(1) == 256, "w4 must be (5,256)");
-    torch::Tensor logits, amax;
+    torch::Tensor logits, amax, qv;
     float* lp = nullptr;
     uint8_t* ap = nullptr;
+    uint8_t* qp = nullptr;
     if (want_logits) {
         logits = torch::empty({B, T, 5}, hseq.options().dtype(torch::kFloat32));
         lp = logits.data_ptr<float>();
@@ -449,11 +460,16 @@ std::vector<torch::Tensor> head_fwd(torch::Tensor hseq, torch::Tensor w4,
         amax = torch::empty({B, T}, hseq.options().dtype(torch::kUInt8));
         ap = amax.data_ptr<uint8_t>();
     }
+    if (want_quality) {
+        qv = torch::empty({B, T, 5}, hseq.options().dtype(torch::kUInt8));
+        qp = qv.data_ptr<uint8_t>();
+    }
     rk::head_fwd(hseq.data_ptr(), w4.data_ptr(), b4.data_ptr<float>(), lp, ap,
-                 T, B, cur_stream());
+                 T, B, cur_stream(), qp);
     std::vector<torch::Tensor> out;
     if (want_logits) out.push_back(logits);
     if (want_argmax) out.push_back(amax);
+    if (want_quality) out.push_back(qv);
     return out;
 }
 
@@ -768,6 +784,60 @@ void vote_consensus(torch::Tensor table, int64_t n_slots, torch::Tensor maj) {
     check_launch("vote kernel");
 }
 
+// the quality table beside a count table: int64 on the Python side, one
+// word per slot; the consensus kernel reads it in 16-byte pairs
+uint64_t* vote_qsum_ptr(const torch::Tensor& qsum, int64_t n_slots) {
+    check(qsum, torch::kInt64, "qsum");
+    TORCH_CHECK(n_slots <= qsum.numel(), "n_slots exceeds the qsum table");
+    return reinterpret_cast<uint64_t*>(qsum.data_ptr<int64_t>());
+}
+
+// vote_scatter plus the five quality units (preds.shape + (5,)) u8 of every
+// column summed into `qsum`
+void vote_scatter_q(torch::Tensor preds, torch::Tensor units,
+                    torch::Tensor positions, torch::Tensor table,
+                    torch::Tensor qsum, int64_t n_slots,
+                    torch::Tensor err_flag) {
+    check(preds, torch::kUInt8, "preds");
+    check(units, torch::kUInt8, "units");
+    check(positions, torch::kInt32, "positions");
+    TORCH_CHECK(positions.dim() >= 1 && positions.size(-1) == 2 &&
+                    positions.numel() == 2 * preds.numel(),
+                "positions must be preds.shape + (2,)");
+    TORCH_CHECK(units.dim() >= 1 && units.size(-1) == 5 &&
+                    units.numel() == 5 * preds.numel(),
+                "units must be preds.shape + (5,)");
+    TORCH_CHECK(preds.numel() < (int64_t(1) << 31), "batch too large");
+    rk::vote_scatter_q(preds.data_ptr<uint8_t>(), units.data_ptr<uint8_t>(),
+                       positions.data_ptr<int32_t>(),
+                       vote_table_ptr(table, n_slots),
+                       vote_qsum_ptr(qsum, n_slots), n_slots,
+                       vote_err_ptr(err_flag), (int)preds.numel(),
+                       cur_stream());
+    check_launch("vote kernel");
+}
+
+// (table, qsum) -> maj (n_slots) u8 as vote_consensus, and qual (n_slots) u8:
+// Phred of the majority class, 0xFF where no votes
+void vote_consensus_q(torch::Tensor table, torch::Tensor qsum,
+                      int64_t n_slots, torch::Tensor maj, torch::Tensor qual) {
+    check(maj, torch::kUInt8, "maj");
+    check(qual, torch::kUInt8, "qual");
+    TORCH_CHECK(maj.numel() >= n_slots && qual.numel() >= n_slots,
+                "maj or qual shorter than n_slots");
+    uint32_t* tab = vote_table_ptr(table, n_slots);
+    uint64_t* qs = vote_qsum_ptr(qsum, n_slots);
+    auto aligned = [](const void* p, uintptr_t a) {
+        return reinterpret_cast<uintptr_t>(p) % a == 0;
+    };
+    TORCH_CHECK(aligned(tab, 16) && aligned(qs, 16) &&
+                    aligned(maj.data_ptr(), 4) && aligned(qual.data_ptr(), 4),
+                "vote tables must be 16-byte and outputs 4-byte aligned");
+    rk::vote_consensus_q(tab, qs, n_slots, maj.data_ptr<uint8_t>(),
+                         qual.data_ptr<uint8_t>(), cur_stream());
+    check_launch("vote kernel");
+}
+
 // ---------------------------------------------------------------------------
 // Device window builder (windows.hip): a region's packed reads -> (x (n, 200,
 // 90) u8, pos (n, 90, 2) i32) on the current stream. The u32 offset and CIGAR
@@ -904,6 +974,9 @@ struct ServeSlot {
     torch::Tensor xg;        // (90*B, 768) bf16 per-layer gate inputs
     torch::Tensor hseq;      // (90, B, 2, 128) bf16 per-layer output
     torch::Tensor amax;      // (B, 90) u8 fused-argmax predictions
+    torch::Tensor qv;        // (B, 90, 5) u8 quality units; `quality` only
+    bool quality = false;    // fixed at construction, so one captured graph
+                             // per mode serves the slot's whole life
     torch::Tensor host_out;  // (B, 90) u8 pinned
     torch::Tensor seq2d, hseq2d, xg2d;  // cached views for addmm_out
     int B;
@@ -976,8 +1049,9 @@ struct ServeSlot {
     hipGraphExec_t votes_gexec = nullptr;
     bool votes_capture_failed = false;
 
-    ServeSlot(py::dict w, int B_, torch::Tensor host_out_, int parts_ = 1)
-        : B(B_), parts(parts_),
+    ServeSlot(py::dict w, int B_, torch::Tensor host_out_, int parts_ = 1,
+              bool quality_ = false)
+        : quality(quality_), B(B_), parts(parts_),
           stream(at::cuda::getStreamFromPool(/*high_priority=*/false)) {
         namespace t = torch;
         TORCH_CHECK(parts >= 1 && parts <= 64 && B % parts == 0,
@@ -1032,6 +1106,7 @@ struct ServeSlot {
         hseq = t::empty({90, B, 2, 128}, dev.dtype(t::kBFloat16));
         if (use_fold) hseq2 = t::empty({90, B, 2, 128}, dev.dtype(t::kBFloat16));
         amax = t::empty({B, 90}, dev.dtype(t::kUInt8));
+        if (quality) qv = t::zeros({B, 90, 5}, dev.dtype(t::kUInt8));
         seq2d = seq.view({(int64_t)90 * B, seq_ld});  // lt path: seq_ld 500
         hseq2d = hseq.view({(int64_t)90 * B, 256});
         xg2d = xg;
@@ -1102,7 +1177,8 @@ struct ServeSlot {
             }
         }
         rk::head_fwd(hseq.data_ptr(), w4.data_ptr(), b4.data_ptr<float>(),
-                     nullptr, amax.data_ptr<uint8_t>(), 90, B, s);
+                     nullptr, amax.data_ptr<uint8_t>(), 90, B, s,
+                     quality ? qv.data_ptr<uint8_t>() : nullptr);
     }
 
     // capture the model body (plus the prediction D2H when `d2h`) into
@@ -1166,7 +1242,8 @@ struct ServeSlot {
                               nullptr, 90, B, s, 0);
         }
         rk::head_fwd(hseq.data_ptr(), w4.data_ptr(), b4.data_ptr<float>(),
-                     nullptr, amax.data_ptr<uint8_t>(), 90, B, s);
+                     nullptr, amax.data_ptr<uint8_t>(), 90, B, s,
+                     quality ? qv.data_ptr<uint8_t>() : nullptr);
     }
 
     // input half of a submit: order the slot stream behind the producer of
@@ -1296,10 +1373,17 @@ struct ServeSlot {
     // table from their own streams; the adds are atomic. The caller keeps
     // x/pos (pinned staging) untouched until sync(), and waits for every
     // slot's ev_done before reading the table.
+    // With `qsum` (a quality slot only) the fused scatter also sums the
+    // head's quality units into it.
     void submit_votes(torch::Tensor x, torch::Tensor pos, int64_t n,
                       torch::Tensor table, int64_t n_slots,
-                      torch::Tensor err_flag) {
+                      torch::Tensor err_flag,
+                      c10::optional<torch::Tensor> qsum) {
         TORCH_CHECK(parts == 1, "votes mode needs an uncoalesced slot");
+        TORCH_CHECK(!qsum.has_value() || quality,
+                    "a qsum table needs a slot built with quality=True");
+        uint64_t* qs = qsum.has_value() ? vote_qsum_ptr(*qsum, n_slots)
+                                        : nullptr;
         TORCH_CHECK(x.scalar_type() == torch::kUInt8 && x.is_contiguous() &&
                         n >= 0 && n <= B && x.numel() >= n * 200 * 90,
                     "x must be contiguous u8 with n <= slot batch rows");
@@ -1320,6 +1404,9 @@ struct ServeSlot {
             if (t->is_cuda())
                 c10::cuda::CUDACachingAllocator::recordStream(
                     t->storage().data_ptr(), stream);
+        if (qs)
+            c10::cuda::CUDACachingAllocator::recordStream(
+                qsum->storage().data_ptr(), stream);
         at::cuda::CUDAStreamGuard guard(stream);
         hipStream_t s = stream.stream();
         if (n > 0) {
@@ -1344,9 +1431,15 @@ struct ServeSlot {
         } else {
             enqueue_model_lt(s);
         }
-        rk::vote_scatter(amax.data_ptr<uint8_t>(),
-                         pos_buf.data_ptr<int32_t>(), tab, n_slots, err,
-                         B * 90, s);
+        if (qs)
+            rk::vote_scatter_q(amax.data_ptr<uint8_t>(),
+                               qv.data_ptr<uint8_t>(),
+                               pos_buf.data_ptr<int32_t>(), tab, qs, n_slots,
+                               err, B * 90, s);
+        else
+            rk::vote_scatter(amax.data_ptr<uint8_t>(),
+                             pos_buf.data_ptr<int32_t>(), tab, n_slots, err,
+                             B * 90, s);
         ++n_runs;
         (void)hipEventRecord(ev_done, stream.stream());
     }
@@ -1440,13 +1533,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("emb"), py::arg("seed"), py::arg("keep"),
           py::arg("phase_mask") = 0x1F, py::arg("seed_buf") = c10::nullopt);
     m.def("head_fwd", &head_fwd, py::arg("hseq"), py::arg("w4"), py::arg("b4"),
-          py::arg("want_logits") = true, py::arg("want_argmax") = false);
+          py::arg("want_logits") = true, py::arg("want_argmax") = false,
+          py::arg("want_quality") = false);
     m.def("cu_masked_stream", &cu_masked_stream, py::arg("reserve_cus"));
     m.def("vote_scatter", &vote_scatter, py::arg("preds"),
           py::arg("positions"), py::arg("table"), py::arg("n_slots"),
           py::arg("err_flag"));
     m.def("vote_consensus", &vote_consensus, py::arg("table"),
           py::arg("n_slots"), py::arg("maj"));
+    m.def("vote_scatter_q", &vote_scatter_q, py::arg("preds"),
+          py::arg("units"), py::arg("positions"), py::arg("table"),
+          py::arg("qsum"), py::arg("n_slots"), py::arg("err_flag"));
+    m.def("vote_consensus_q", &vote_consensus_q, py::arg("table"),
+          py::arg("qsum"), py::arg("n_slots"), py::arg("maj"),
+          py::arg("qual"));
     m.def("build_windows", &build_windows, py::arg("ref_start"),
           py::arg("ref_end"), py::arg("reverse"), py::arg("cigar_off"),
           py::arg("seq_off"), py::arg("cigar"), py::arg("seq4"),
@@ -1454,9 +1554,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("ncols_max"), py::arg("rows"), py::arg("cols"),
           py::arg("stride"), py::arg("max_ins"));
     py::class_<ServeSlot>(m, "ServeSlot")
-        .def(py::init<py::dict, int, torch::Tensor, int>(),
+        .def(py::init<py::dict, int, torch::Tensor, int, bool>(),
              py::arg("weights"), py::arg("batch"), py::arg("host_out"),
-             py::arg("parts") = 1)
+             py::arg("parts") = 1, py::arg("quality") = false)
         .def("run", &ServeSlot::run, py::arg("x"), py::arg("n"))
         .def("submit", &ServeSlot::submit, py::arg("x"), py::arg("n"),
              py::call_guard<py::gil_scoped_release>())
@@ -1473,7 +1573,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("submit_votes", &ServeSlot::submit_votes, py::arg("x"),
              py::arg("pos"), py::arg("n"), py::arg("table"),
              py::arg("n_slots"), py::arg("err_flag"),
+             py::arg("qsum") = c10::nullopt,
              py::call_guard<py::gil_scoped_release>())
         .def_readonly("amax", &ServeSlot::amax)
+        .def_readonly("qv", &ServeSlot::qv)
+        .def_readonly("quality", &ServeSlot::quality)
         .def_readonly("host_out", &ServeSlot::host_out);
 }

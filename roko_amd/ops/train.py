@@ -48,7 +48,12 @@ _WGRAD_BUFS: dict = {}
 
 def _wgrad_bufs(key, dev, *shapes):
     """key -> {'pp': int, 'sets': [tuple(tensors), tuple(tensors)]}.
-    shapes: (name, *dims) per output tensor; returns the next set."""
+    shapes: (name, *dims) per output tensor; returns the next set.
+    Callers key by id(parameter), and CPython reuses the id of a freed
+    model's parameter for an unrelated one of the next model in the process,
+    so the shapes and the device are part of the key: a reused id with other
+    shapes gets buffers of its own."""
+    key = (key, dev, shapes)
     ent = _WGRAD_BUFS.get(key)
     if ent is None:
         mk = lambda dims: torch.empty(*dims, device=dev, dtype=torch.float32)

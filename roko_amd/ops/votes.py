@@ -11,6 +11,13 @@ ins, five 4-bit class counters per word (16 B per draft base). The window
 extractor gives a column at most 6 votes (docs/KERNELS.md), so 4 bits hold
 it; a counter that would pass 15 sets an error flag and `counts()` /
 `consensus()` raise instead of returning a corrupted table.
+
+Quality (`quality=True`, roko_amd/quality.py): a second table `qsum` beside
+each count table, one 64-bit word per slot (8 B per slot, 32 B per draft
+base), class k in the 12-bit field at bits [12k, 12k+12) holding the sum of
+that class's quarter-Phred units over the slot's votes. 16 votes x 255 = 4080
+< 4096, so whatever the count table holds fits; a field that would pass 4095
+sets the same overflow flag.
 """
 
 from __future__ import annotations
@@ -25,13 +32,15 @@ from .. import config as C
 SLOTS_PER_POS = C.MAX_INS + 1
 _KEY_SHIFT = 3  # VoteTable key = pos << 3 | ins (inference.py)
 _NIBBLE = 4
+_QFIELD = 12  # bits per class in a qsum word
 _ERR_RANGE = 1
 _ERR_OVERFLOW = 2
 
 
 class VoteOverflowError(RuntimeError):
     """A column received more votes for one class than a 4-bit counter
-    holds; the device table is not usable."""
+    holds, or more quality units than a 12-bit field holds; the device
+    tables are not usable."""
 
 
 class DeviceVotes:
@@ -43,20 +52,29 @@ class DeviceVotes:
     through its serving slots in votes mode: fill `staging()`, then
     `add_batch(contig, n)`.
     `scatter()` adds given predictions directly (tests, merging).
+    With `quality=True` (and a pipe built with quality=True) every vote
+    also adds its quality units into the contig's `qsum` table.
     """
 
     def __init__(self, contig_lens: Dict[str, int], pipe=None,
-                 device: Optional[torch.device] = None):
+                 device: Optional[torch.device] = None,
+                 quality: bool = False):
         from . import ext
 
         self.ext = ext()
         self.lens = dict(contig_lens)
         self.pipe = pipe
+        self.quality = bool(quality)
+        if self.quality and pipe is not None and \
+                not getattr(pipe, "quality", False):
+            raise ValueError("quality votes need a pipeline built with "
+                             "quality=True")
         if device is None:
             device = (next(pipe.model.parameters()).device if pipe is not None
                       else torch.device("cuda", torch.cuda.current_device()))
         self.device = device
         self.tables: Dict[str, torch.Tensor] = {}
+        self.qsums: Dict[str, torch.Tensor] = {}
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=device)
         self._stage = None
 
@@ -70,7 +88,19 @@ class DeviceVotes:
             t = torch.zeros(self.n_slots(contig), dtype=torch.int32,
                             device=self.device)
             self.tables[contig] = t
+            if self.quality:
+                self.qsums[contig] = torch.zeros(
+                    self.n_slots(contig), dtype=torch.int64,
+                    device=self.device)
         return t
+
+    def qsum(self, contig: str) -> Optional[torch.Tensor]:
+        """The contig's quality table (allocated with its count table), or
+        None without quality."""
+        if not self.quality:
+            return None
+        self.table(contig)
+        return self.qsums[contig]
 
     def has_votes(self, contig: str) -> bool:
         return contig in self.tables
@@ -78,6 +108,7 @@ class DeviceVotes:
     def free(self, contig: str) -> None:
         self.drain()
         self.tables.pop(contig, None)
+        self.qsums.pop(contig, None)
 
     def _validate(self, contig: str, positions: np.ndarray) -> None:
         """Host-side range check before anything is uploaded; the kernel's
@@ -107,7 +138,7 @@ class DeviceVotes:
         self._validate(contig, self._stage[1][:n])
         self._stage = None
         self.pipe.submit_votes(n, self.table(contig), self.n_slots(contig),
-                               self.err_flag)
+                               self.err_flag, self.qsum(contig))
 
     def add_device_batch(self, contig: str, x: torch.Tensor,
                          pos: torch.Tensor, n: int) -> None:
@@ -117,17 +148,33 @@ class DeviceVotes:
         drops and flags an out-of-range position, and `_check()` raises on
         that flag before any table is read."""
         self.pipe.submit_votes_device(x, pos, n, self.table(contig),
-                                      self.n_slots(contig), self.err_flag)
+                                      self.n_slots(contig), self.err_flag,
+                                      self.qsum(contig))
 
-    def scatter(self, contig: str, preds, positions) -> None:
+    def scatter(self, contig: str, preds, positions, units=None) -> None:
         """Add given predictions (N, W) u8 at positions (N, W, 2) i32 on the
-        current stream. Rows with pos < 0 do not vote."""
+        current stream. Rows with pos < 0 do not vote. With quality, `units`
+        (N, W, 5) u8 are the votes' quality units."""
         positions = np.ascontiguousarray(positions, dtype=np.int32)
         preds = np.ascontiguousarray(preds, dtype=np.uint8)
         live = positions[positions[..., 0] >= 0]
         self._validate(contig, live)
         if preds.size and preds.max() >= C.NUM_CLASSES:
             raise ValueError("prediction class outside [0, NUM_CLASSES)")
+        if self.quality != (units is not None):
+            raise ValueError("units are given exactly when the tables were "
+                             "built with quality=True")
+        if units is not None:
+            units = np.ascontiguousarray(units, dtype=np.uint8)
+            if units.shape != preds.shape + (C.NUM_CLASSES,):
+                raise ValueError("units must be preds.shape + (NUM_CLASSES,)")
+            self.ext.vote_scatter_q(
+                torch.from_numpy(preds).to(self.device),
+                torch.from_numpy(units).to(self.device),
+                torch.from_numpy(positions).to(self.device),
+                self.table(contig), self.qsum(contig), self.n_slots(contig),
+                self.err_flag)
+            return
         self.ext.vote_scatter(
             torch.from_numpy(preds).to(self.device),
             torch.from_numpy(positions).to(self.device),
@@ -144,8 +191,10 @@ class DeviceVotes:
         if flag & _ERR_OVERFLOW:
             raise VoteOverflowError(
                 "device vote table overflow: a column received more than 15 "
-                "votes for one class (4-bit counters); rerun with host votes "
-                "(votes='host')")
+                "votes for one class (4-bit counters)"
+                + (" or more quality units than a 12-bit field holds"
+                   if self.quality else "")
+                + "; rerun with host votes (votes='host')")
         if flag & _ERR_RANGE:
             raise RuntimeError(
                 "device vote kernel dropped an out-of-range position or "
@@ -170,3 +219,36 @@ class DeviceVotes:
         maj = torch.empty(n, dtype=torch.uint8, device=self.device)
         self.ext.vote_consensus(self.table(contig), n, maj)
         return maj.cpu().numpy()
+
+    def _need_quality(self) -> None:
+        if not self.quality:
+            raise RuntimeError("these tables were built without quality "
+                               "(DeviceVotes(..., quality=True))")
+
+    def sums(self, contig: str) -> Tuple[np.ndarray, np.ndarray]:
+        """Unpack the quality table to the host form of
+        quality.accumulate_quality: (keys int64 sorted, sums int64 (K,
+        NUM_CLASSES)) over the voted slots, the keys of `counts()`."""
+        self._need_quality()
+        self._check()
+        tab = self.table(contig).cpu().numpy().view(np.uint32)
+        q = self.qsum(contig).cpu().numpy().view(np.uint64)
+        slots = np.flatnonzero(tab)
+        keys = ((slots // SLOTS_PER_POS) << _KEY_SHIFT) | (slots % SLOTS_PER_POS)
+        shifts = np.arange(C.NUM_CLASSES, dtype=np.uint64) * np.uint64(_QFIELD)
+        sums = (q[slots, None] >> shifts[None, :]) \
+            & np.uint64((1 << _QFIELD) - 1)
+        return keys.astype(np.int64), sums.astype(np.int64)
+
+    def consensus_quality(self, contig: str) -> Tuple[np.ndarray, np.ndarray]:
+        """(maj, qual) per slot, both uint8: `consensus()` and the Phred of
+        the majority class (quality.NO_QUAL = 0xFF where no votes). One
+        kernel and two bytes per slot of D2H."""
+        self._need_quality()
+        self._check()
+        n = self.n_slots(contig)
+        maj = torch.empty(n, dtype=torch.uint8, device=self.device)
+        qual = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self.ext.vote_consensus_q(self.table(contig), self.qsum(contig), n,
+                                  maj, qual)
+        return maj.cpu().numpy(), qual.cpu().numpy()

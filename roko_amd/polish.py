@@ -2,7 +2,7 @@
 
   python -m roko_amd.polish <draft.fasta> <reads.bam> <model.pth> <out.fasta>
       [--t workers] [--b batch] [--seed N] [--extract host|device]
-      [--sampler mt19937|counter]
+      [--sampler mt19937|counter] [--fastq out.fastq]
 
 Does what `features` followed by `inference` does, and writes the same FASTA
 byte for byte, without the RKW file between them: region windows stream from
@@ -18,6 +18,12 @@ With --extract device the workers only inflate, filter and pack the reads
 window ever exists on the host. That route samples rows with the counter
 sampler whatever --sampler says; `--extract host --sampler counter` writes
 the same FASTA.
+
+With --fastq PATH a FASTQ is written as well: the same sequences with a Phred
+quality per polished base (roko_amd/quality.py), computed on the device on
+every GPU route and by the numpy reference on the CPU route. Draft bases that
+are copied through unpolished get Q0; a deleted base leaves no trace in the
+quality string.
 
 Single process only; for multi-GPU runs use `features` + `inference` under
 torchrun.
@@ -35,7 +41,7 @@ import numpy as np
 from . import config as C
 from .config import FeatureConfig
 from .features import generate_infer, generate_reads, generate_regions
-from .io.fasta import read_fasta, write_fasta
+from .io.fasta import read_fasta, write_fasta, write_fastq
 
 # NOTE: torch (and everything that imports it) is imported inside polish():
 # spawned extractor workers re-import this module when it is the program's
@@ -51,15 +57,20 @@ class _DeviceSink:
     are packed into the slots' pinned staging with slice copies; a contig is
     stitched from its consensus bytes as soon as its last region is in."""
 
-    def __init__(self, model, batch: int, depth: int, lens: Dict[str, int]):
+    def __init__(self, model, batch: int, depth: int, lens: Dict[str, int],
+                 quality: bool = False):
         from .ops.forward import InferencePipeline
         from .ops.votes import DeviceVotes
 
         self.batch = batch
+        self.quality = quality
+        self.quals: Dict[str, str] = {}  # contig -> quality string
         # votes mode runs one batch per slot (coalesce=1)
         self.dv = DeviceVotes(lens, InferencePipeline(model, batch,
                                                       depth=depth,
-                                                      coalesce=1))
+                                                      coalesce=1,
+                                                      quality=quality),
+                              quality=quality)
         self.x = self.pos = None
         self.fill = 0
 
@@ -89,6 +100,13 @@ class _DeviceSink:
             self._submit(contig)  # a slot batch votes into one contig's table
         if not self.dv.has_votes(contig):
             return draft
+        if self.quality:
+            from .quality import stitch_dense_qual
+
+            maj, qual = self.dv.consensus_quality(contig)  # drains first
+            self.dv.free(contig)
+            seq, self.quals[contig] = stitch_dense_qual(draft, maj, qual)
+            return seq
         maj = self.dv.consensus(contig)  # drains the pipeline first
         self.dv.free(contig)
         return stitch_dense(draft, maj)
@@ -102,8 +120,9 @@ class _DeviceBuildSink(_DeviceSink):
     slots in votes mode, device to device, in slices of at most `batch`
     windows. A region's last slice may be short."""
 
-    def __init__(self, model, batch, depth, lens, cfg, device):
-        super().__init__(model, batch, depth, lens)
+    def __init__(self, model, batch, depth, lens, cfg, device,
+                 quality=False):
+        super().__init__(model, batch, depth, lens, quality)
         self.cfg, self.device = cfg, device
 
     def add_reads(self, contig: str, pack: dict) -> int:
@@ -124,12 +143,20 @@ class _HostSink:
     across contig boundaries), so both routes run the model on identical
     batches. Contigs are stitched at the end."""
 
-    def __init__(self, model, batch: int, device, drafts: Dict[str, str]):
+    def __init__(self, model, batch: int, device, drafts: Dict[str, str],
+                 quality: bool = False):
         from .inference import StreamingVotes
 
         self.model, self.batch, self.device = model, batch, device
         self.drafts = drafts
-        self.sv = StreamingVotes()
+        self.quality = quality
+        self.quals: Dict[str, str] = {}  # contig -> quality string
+        if quality:
+            from .quality import StreamingQualityVotes
+
+            self.sv = StreamingQualityVotes()
+        else:
+            self.sv = StreamingVotes()
         self.buf: List[tuple] = []  # (contig, positions, examples) chunks
         self.n = 0
 
@@ -156,10 +183,18 @@ class _HostSink:
         with torch.no_grad():
             logits = self.model(x.to(self.device).long())
         preds = logits.argmax(dim=2).to(torch.uint8).cpu().numpy()
+        if self.quality:
+            from .quality import phred_units
+
+            units = phred_units(logits.cpu().numpy())
         row = 0
         for contig, p, _ in take:
             for j in range(len(p)):  # StreamingVotes takes single windows
-                self.sv.add(contig, np.asarray(p[j]), preds[row + j])
+                if self.quality:
+                    self.sv.add(contig, np.asarray(p[j]), preds[row + j],
+                                units[row + j])
+                else:
+                    self.sv.add(contig, np.asarray(p[j]), preds[row + j])
             row += len(p)
 
     def finish_contig(self, contig: str, draft: str) -> Optional[str]:
@@ -170,9 +205,22 @@ class _HostSink:
 
         if self.n:
             self._run(self.n)
-        tables = self.sv.finalize()
-        return {name: stitch_contig(self.drafts[name], *tables[name])
-                for name in tables}
+        if not self.quality:
+            tables = self.sv.finalize()
+            return {name: stitch_contig(self.drafts[name], *tables[name])
+                    for name in tables}
+        from .quality import stitch_tables
+
+        tables, sums = self.sv.finalize()
+        out = {}
+        for name in tables:
+            out[name] = stitch_contig(self.drafts[name], *tables[name])
+            seq, self.quals[name] = stitch_tables(self.drafts[name],
+                                                  tables[name], sums[name])
+            if seq != out[name]:
+                raise RuntimeError(f"{name}: the quality stitch disagrees "
+                                   "with the sequence stitch")
+        return out
 
 
 def polish(
@@ -188,9 +236,11 @@ def polish(
     log=print,
     depth: int = 16,
     extract: str = "host",
+    out_fastq: Optional[str] = None,
 ) -> Dict[str, str]:
     """Polish `draft_fasta` with the reads in `reads_bam`; returns {contig:
-    polished sequence} and writes FASTA if `out_fasta` is given. Regions,
+    polished sequence} and writes FASTA if `out_fasta` is given, and FASTQ
+    with a Phred quality per polished base if `out_fastq` is. Regions,
     FeatureConfig and seeding are those of `features.run`; `depth` is the
     number of in-flight batches on the GPU. `extract="device"` builds the
     windows on the GPU from packed reads (counter sampler, whatever
@@ -222,7 +272,8 @@ def polish(
         pool = multiprocessing.get_context("spawn").Pool(processes=workers)
     try:
         return _polish(refs, jobs, pool, model_path, out_fasta, workers,
-                       batch_size, device, model, log, depth, extract, cfg)
+                       batch_size, device, model, log, depth, extract, cfg,
+                       out_fastq)
     finally:
         if pool is not None:
             pool.terminate()
@@ -239,7 +290,8 @@ def _device_type(device) -> str:
 
 
 def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
-            device, model, log, depth, extract, cfg) -> Dict[str, str]:
+            device, model, log, depth, extract, cfg,
+            out_fastq=None) -> Dict[str, str]:
     import torch
 
     from .model import RokoModel
@@ -253,14 +305,16 @@ def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
     model = model.to(device).eval()
 
     drafts = dict(refs)
+    quality = bool(out_fastq)
     if extract == "device":
         sink = _DeviceBuildSink(model, batch_size, depth,
-                                {n: len(s) for n, s in refs}, cfg, device)
+                                {n: len(s) for n, s in refs}, cfg, device,
+                                quality)
     elif device.type == "cuda":
         sink = _DeviceSink(model, batch_size, depth,
-                           {n: len(s) for n, s in refs})
+                           {n: len(s) for n, s in refs}, quality)
     else:
-        sink = _HostSink(model, batch_size, device, drafts)
+        sink = _HostSink(model, batch_size, device, drafts, quality)
     worker = generate_reads if extract == "device" else generate_infer
     log(f"polish: {len(jobs)} region jobs, {workers} workers, "
         f"batch {batch_size}, windows on {extract}, votes on {device.type}")
@@ -313,6 +367,16 @@ def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
     if out_fasta:
         write_fasta(out_fasta, sorted(out.items()))
         log(f"wrote {len(out)} polished contigs to {out_fasta}")
+    if out_fastq:
+        from .quality import unpolished_quality
+
+        # a contig the sink gave no qualities for came through as draft
+        write_fastq(out_fastq,
+                    [(name, seq,
+                      sink.quals.get(name) or unpolished_quality(seq))
+                     for name, seq in sorted(out.items())])
+        log(f"wrote {len(out)} polished contigs with qualities to "
+            f"{out_fastq}")
     return out
 
 
@@ -332,10 +396,13 @@ def main(argv=None):
     p.add_argument("--sampler", choices=("mt19937", "counter"),
                    default="mt19937",
                    help="row sampler of --extract host (device: counter)")
+    p.add_argument("--fastq", default=None, metavar="PATH",
+                   help="also write FASTQ: the same sequences with a Phred "
+                        "quality per polished base")
     a = p.parse_args(argv)
     polish(a.draft, a.bam, a.model, a.out, workers=a.t, batch_size=a.b,
            cfg=FeatureConfig(seed=a.seed, sampler=a.sampler),
-           extract=a.extract)
+           extract=a.extract, out_fastq=a.fastq)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 
   python scripts/polish_bench.py [--ref-len N] [--cov C] [--t WORKERS]
       [--b BATCH] [--limit SECONDS] [--dir DIR] [--routes a,b,...]
-      [--repeat N]
+      [--repeat N] [--fastq]
 
 Builds a synthetic assembly (the generators of tests/test_gpu_e2e.py::
 _make_case, size given by --ref-len), then times
@@ -24,6 +24,13 @@ of wall time), and for the file routes the split between extraction and
 inference. A last line says whether the FASTA files of the routes that ran
 are identical within each sampler (the two samplers draw different rows).
 The model is randomly initialised: rates do not depend on the weights.
+
+--fastq makes every route but two_step (host votes) also write a FASTQ with
+per-base qualities, which on the GPU turns on the quality output of the head
+kernel, the fused vote scatter and the quality consensus; each JSON line then
+carries "fastq": true and the device memory the quality tables add (8 bytes
+per column slot, 32 per draft base). Run once with and once without to see
+what the feature costs.
 """
 
 import argparse
@@ -65,7 +72,7 @@ def make_case(d, ref_len, cov, seed=7):
     return len(es.draft)
 
 
-def run_step(step, d, workers, batch, region):
+def run_step(step, d, workers, batch, region, fastq=False):
     """One route, in this (child) process; prints its JSON line."""
     from roko_amd import config as C
     from roko_amd.config import FeatureConfig
@@ -83,6 +90,11 @@ def run_step(step, d, workers, batch, region):
     draft_bases = sum(len(s) for _, s in read_fasta(draft))
     rec = {"step": step, "workers": workers, "batch": batch,
            "draft_bases": draft_bases}
+    out_fastq = None
+    if fastq and step != "two_step":
+        out_fastq = os.path.join(d, f"{step}.fastq")
+        rec.update(fastq=True,
+                   qsum_bytes=8 * (C.MAX_INS + 1) * draft_bases)
     t0 = time.time()
     if step.startswith("polish"):
         from roko_amd.polish import LAST_RUN
@@ -91,7 +103,8 @@ def run_step(step, d, workers, batch, region):
             cfg.sampler = "counter"
         polish(draft, bam, ckpt, out, workers=workers, batch_size=batch,
                cfg=cfg, log=quiet,
-               extract="device" if step == "polish_device" else "host")
+               extract="device" if step == "polish_device" else "host",
+               out_fastq=out_fastq)
         n = LAST_RUN["windows"]
     else:
         rkw = os.path.join(d, f"{step}.rkw")
@@ -99,7 +112,8 @@ def run_step(step, d, workers, batch, region):
         rec["features_s"] = round(time.time() - t0, 3)
         t1 = time.time()
         infer(rkw, ckpt, out, batch_size=batch, log=quiet,
-              votes="host" if step == "two_step" else "device")
+              votes="host" if step == "two_step" else "device",
+              out_fastq=out_fastq)
         rec["infer_s"] = round(time.time() - t1, 3)
     wall = time.time() - t0
     rec.update(windows=n, wall_s=round(wall, 3),
@@ -124,11 +138,14 @@ def main():
                    help="comma-separated routes to run, in this order")
     p.add_argument("--repeat", type=int, default=1,
                    help="run the chosen routes this many times, in turn")
+    p.add_argument("--fastq", action="store_true",
+                   help="also write FASTQ (per-base qualities) on every "
+                        "route but two_step")
     p.add_argument("--step", choices=ALL_STEPS, default=None,
                    help="(internal) run one route in this process")
     a = p.parse_args()
     if a.step:
-        run_step(a.step, a.dir, a.t, a.b, a.region)
+        run_step(a.step, a.dir, a.t, a.b, a.region, a.fastq)
         return
 
     import torch
@@ -151,6 +168,8 @@ def main():
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable,
                os.path.abspath(__file__), "--step", step, "--dir", d,
                "--t", str(a.t), "--b", str(a.b), "--region", str(a.region)]
+        if a.fastq:
+            cmd.append("--fastq")
         rc = subprocess.call(cmd)
         if rc != 0:
             print(json.dumps({"step": step, "failed": rc}), flush=True)
@@ -162,6 +181,11 @@ def main():
                  for s in group if s in routes}
         if blobs:
             rec[key] = len(blobs) == 1
+        if a.fastq:
+            blobs = {open(os.path.join(d, f"{s}.fastq"), "rb").read()
+                     for s in group if s in routes and s != "two_step"}
+            if blobs:
+                rec[key + "_fastq"] = len(blobs) == 1
     print(json.dumps(rec), flush=True)
 
 
