@@ -118,6 +118,17 @@ void windows_fill(const int32_t* ref_start, const int32_t* ref_end,
                   const int32_t* wpre, const int32_t* nvalid,
                   const int32_t* out_idx, uint64_t region_key, int n_all,
                   int n_out, uint8_t* x, int32_t* pos, hipStream_t stream);
+void truth_scan(const int32_t* ref_start, const int32_t* ref_end,
+                const uint32_t* cigar_off, const uint32_t* seq_off,
+                const uint32_t* cigar, const uint8_t* seq4, int32_t* op_rpos,
+                int32_t* op_qpos, int n, int32_t* err, hipStream_t stream);
+void label_windows(const int32_t* ref_start, const int32_t* ref_end,
+                   const uint32_t* cigar_off, const uint32_t* seq_off,
+                   const uint32_t* cigar, const uint8_t* seq4,
+                   int32_t* op_rpos, int32_t* op_qpos, int n, int index,
+                   int lo, int hi, const int32_t* pos, int n_windows,
+                   uint8_t* labels, uint8_t* keep, int32_t* err,
+                   hipStream_t stream);
 }  // namespace rk
 
 namespace {
@@ -946,6 +957,98 @@ std::vector<torch::Tensor> build_windows(
 }
 
 // ---------------------------------------------------------------------------
+// Truth labels (windows.hip). A truth pack is a contig's truth alignments in
+// the read pack's layout, uploaded once; ops/labels_device.py has checked the
+// offsets against the array lengths, as for build_windows.
+static int64_t check_truth_pack(const torch::Tensor& ref_start,
+                                const torch::Tensor& ref_end,
+                                const torch::Tensor& cigar_off,
+                                const torch::Tensor& seq_off,
+                                const torch::Tensor& cigar,
+                                const torch::Tensor& seq4) {
+    check(ref_start, torch::kInt32, "ref_start");
+    check(ref_end, torch::kInt32, "ref_end");
+    check(cigar_off, torch::kInt32, "cigar_off");
+    check(seq_off, torch::kInt32, "seq_off");
+    check(cigar, torch::kInt32, "cigar");
+    check(seq4, torch::kUInt8, "seq4");
+    const int64_t n = ref_start.numel();
+    TORCH_CHECK(ref_end.numel() == n && cigar_off.numel() == n + 1 &&
+                    seq_off.numel() == n + 1,
+                "per-alignment arrays disagree on the number of alignments");
+    TORCH_CHECK(n < (int64_t(1) << 31) && cigar.numel() < (int64_t(1) << 31) &&
+                    seq4.numel() < (int64_t(1) << 31),
+                "truth pack too large");
+    return n;
+}
+
+// -> [op_rpos, op_qpos, err (n)]: the per-op scan of every alignment and its
+// refusal bits (1: zero-length op, 2: S/H/P between aligned ops).
+std::vector<torch::Tensor> truth_scan(
+    torch::Tensor ref_start, torch::Tensor ref_end, torch::Tensor cigar_off,
+    torch::Tensor seq_off, torch::Tensor cigar, torch::Tensor seq4) {
+    const int64_t n = check_truth_pack(ref_start, ref_end, cigar_off, seq_off,
+                                       cigar, seq4);
+    auto i32 = ref_start.options();
+    auto op_rpos = torch::empty({cigar.numel()}, i32);
+    auto op_qpos = torch::empty({cigar.numel()}, i32);
+    auto err = torch::zeros({n}, i32);
+    auto u32 = [](const torch::Tensor& t) {
+        return reinterpret_cast<const uint32_t*>(t.data_ptr<int32_t>());
+    };
+    rk::truth_scan(ref_start.data_ptr<int32_t>(), ref_end.data_ptr<int32_t>(),
+                   u32(cigar_off), u32(seq_off), u32(cigar),
+                   seq4.data_ptr<uint8_t>(), op_rpos.data_ptr<int32_t>(),
+                   op_qpos.data_ptr<int32_t>(), (int)n,
+                   err.data_ptr<int32_t>(), cur_stream());
+    check_launch("truth scan kernel");
+    return {op_rpos, op_qpos, err};
+}
+
+// pos (n, 90, 2) i32 of built windows, one alignment of the scanned pack and
+// its label span [lo, hi) -> [labels (n, 90) u8, keep (n) u8, err (1) i32]
+// on the current stream. err bit 4: a column outside the span.
+std::vector<torch::Tensor> label_windows(
+    torch::Tensor pos, torch::Tensor ref_start, torch::Tensor ref_end,
+    torch::Tensor cigar_off, torch::Tensor seq_off, torch::Tensor cigar,
+    torch::Tensor seq4, torch::Tensor op_rpos, torch::Tensor op_qpos,
+    int64_t align_index, int64_t lo, int64_t hi) {
+    const int64_t n = check_truth_pack(ref_start, ref_end, cigar_off, seq_off,
+                                       cigar, seq4);
+    check(pos, torch::kInt32, "pos");
+    check(op_rpos, torch::kInt32, "op_rpos");
+    check(op_qpos, torch::kInt32, "op_qpos");
+    TORCH_CHECK(pos.dim() == 3 && pos.size(1) == 90 && pos.size(2) == 2,
+                "pos must be (n, 90, 2)");
+    TORCH_CHECK(op_rpos.numel() == cigar.numel() &&
+                    op_qpos.numel() == cigar.numel(),
+                "the pack is not scanned (truth_scan)");
+    TORCH_CHECK(align_index >= 0 && align_index < n,
+                "align_index out of range");
+    TORCH_CHECK(lo >= 0 && lo <= hi && hi < (int64_t(1) << 31),
+                "label span out of range");
+    const int64_t nw = pos.size(0);
+    TORCH_CHECK(nw < (int64_t(1) << 31) / 90, "too many windows");
+    auto u8 = seq4.options();
+    auto labels = torch::empty({nw, 90}, u8);
+    auto keep = torch::empty({nw}, u8);
+    auto err = torch::zeros({1}, pos.options());
+    auto u32 = [](const torch::Tensor& t) {
+        return reinterpret_cast<const uint32_t*>(t.data_ptr<int32_t>());
+    };
+    rk::label_windows(ref_start.data_ptr<int32_t>(),
+                      ref_end.data_ptr<int32_t>(), u32(cigar_off),
+                      u32(seq_off), u32(cigar), seq4.data_ptr<uint8_t>(),
+                      op_rpos.data_ptr<int32_t>(), op_qpos.data_ptr<int32_t>(),
+                      (int)n, (int)align_index, (int)lo, (int)hi,
+                      pos.data_ptr<int32_t>(), (int)nw,
+                      labels.data_ptr<uint8_t>(), keep.data_ptr<uint8_t>(),
+                      err.data_ptr<int32_t>(), cur_stream());
+    check_launch("label windows kernel");
+    return {labels, keep, err};
+}
+
+// ---------------------------------------------------------------------------
 // Serving fast path: ONE C++ call enqueues the whole b-batch inference
 // forward on a slot-owned HIP stream.
 //
@@ -1553,6 +1656,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("start"), py::arg("end"), py::arg("region_key"),
           py::arg("ncols_max"), py::arg("rows"), py::arg("cols"),
           py::arg("stride"), py::arg("max_ins"));
+    m.def("truth_scan", &truth_scan, py::arg("ref_start"), py::arg("ref_end"),
+          py::arg("cigar_off"), py::arg("seq_off"), py::arg("cigar"),
+          py::arg("seq4"));
+    m.def("label_windows", &label_windows, py::arg("pos"),
+          py::arg("ref_start"), py::arg("ref_end"), py::arg("cigar_off"),
+          py::arg("seq_off"), py::arg("cigar"), py::arg("seq4"),
+          py::arg("op_rpos"), py::arg("op_qpos"), py::arg("align_index"),
+          py::arg("lo"), py::arg("hi"));
     py::class_<ServeSlot>(m, "ServeSlot")
         .def(py::init<py::dict, int, torch::Tensor, int, bool>(),
              py::arg("weights"), py::arg("batch"), py::arg("host_out"),

@@ -40,6 +40,10 @@
 // Zero-length CIGAR ops are not representable here the way the host builder
 // treats them (an `0M` before an I re-attaches the insertion): they set
 // WIN_ERR_ZERO_OP and the caller refuses the region.
+//
+// The end of the file holds the two kernels of the training route, which
+// share the per-cell lookup: truth_scan and label_windows (7, 8) give every
+// column of the built windows its truth label.
 
 #include <cstdint>
 
@@ -514,6 +518,171 @@ void windows_fill(const int32_t* ref_start, const int32_t* ref_end,
                        P, col0, colpos, mask, wpre, nvalid, out_idx,
                        (n + 63) / 64, region_key,
                        reinterpret_cast<uint32_t*>(x), pos, n_out);
+}
+
+// ---------------------------------------------------------------------------
+// Truth labels of built windows (training features). The label of a column
+// (pos, slot) is the truth alignment's base there: the per-cell CIGAR lookup
+// of the read windows, applied to one alignment. labels.get_pos_and_labels
+// plus the lookup of features._generate_train is the oracle; the numpy twin
+// is ops/labels_device.py::label_windows_reference.
+//
+// A truth pack is a contig's truth alignments in the layout of the read pack
+// (no strand). truth_scan runs once per contig; label_windows once per kept
+// alignment of a region.
+
+constexpr uint32_t OP_H = 5, OP_P = 6;
+constexpr uint32_t LABEL_GAP = WB_GAP, LABEL_UNKNOWN = WB_UNKNOWN;
+constexpr int LBL_ERR_ZERO_OP = 1;  // a zero-length CIGAR op
+constexpr int LBL_ERR_CLIP = 2;     // S/H/P between aligned ops, or op > 8
+constexpr int LBL_ERR_RANGE = 4;    // a column outside the label span
+
+RK_DEV bool op_is_clip(uint32_t op) {
+    return op == OP_S || op == OP_H || op == OP_P;
+}
+
+// 7. one wave per truth alignment: the op scan of read_scan_mark, without
+// marks. err[r] collects the alignment's refusal bits.
+__global__ __launch_bounds__(256) void truth_scan_kernel(
+    WinPack P, int32_t* __restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= P.n) return;
+    const uint32_t c0 = P.cigar_off[r], c1 = P.cigar_off[r + 1];
+    // first and last op that is not a clip: clips outside them are the ends
+    uint32_t first = c1, last = c0;
+    for (uint32_t base = c0; base < c1; base += 64) {
+        const uint32_t i = base + lane;
+        const bool body = i < c1 && !op_is_clip(P.cigar[i] & 15u);
+        const unsigned long long m = __ballot(body);
+        if (m) {
+            if (first == c1) first = base + (uint32_t)(__ffsll(m) - 1);
+            last = base + 63u - (uint32_t)__clzll(m);
+        }
+    }
+    int rbase = P.ref_start[r], qbase = 0;
+    unsigned long long zero = 0, clip = 0;
+    for (uint32_t base = c0; base < c1; base += 64) {
+        const uint32_t i = base + lane;
+        const bool live = i < c1;
+        const uint32_t w = live ? P.cigar[i] : 0u;
+        const uint32_t op = w & 15u;
+        const int len = (int)(w >> 4);
+        const int rl = (live && (op_is_match(op) || op == OP_D || op == OP_N))
+                           ? len : 0;
+        const int ql = (live && (op_is_match(op) || op == OP_I || op == OP_S))
+                           ? len : 0;
+        const int ri = wave_incl_scan(rl), qi = wave_incl_scan(ql);
+        const int rpos = rbase + ri - rl, qpos = qbase + qi - ql;
+        rbase += __shfl(ri, 63);
+        qbase += __shfl(qi, 63);
+        zero |= __ballot(live && len == 0);
+        clip |= __ballot(live && (op > OP_X ||
+                                  (op_is_clip(op) && i > first && i < last)));
+        if (!live) continue;
+        P.op_rpos[i] = rpos;
+        P.op_qpos[i] = qpos;
+    }
+    if (lane == 0)
+        err[r] = (zero ? LBL_ERR_ZERO_OP : 0) | (clip ? LBL_ERR_CLIP : 0);
+}
+
+// 8. one workgroup of two waves per window, one lane per column. Alignment r
+// labels the columns; [lo, hi) is its label span (clamped to the alignment
+// here, so no search leaves its ops).
+__global__ __launch_bounds__(128) void label_windows_kernel(
+    WinPack P, const int32_t* __restrict__ pos,  // (n, 90, 2)
+    int r, int lo, int hi, uint8_t* __restrict__ labels,  // (n, 90)
+    uint8_t* __restrict__ keep,                           // (n)
+    int32_t* __restrict__ err) {
+    __shared__ uint32_t s_op[2];
+    __shared__ int s_p[2];
+    const int w = blockIdx.x, tid = threadIdx.x;
+    const uint32_t c0 = P.cigar_off[r], c1 = P.cigar_off[r + 1];
+    lo = max(lo, P.ref_start[r]);
+    hi = min(hi, P.ref_end[r]);
+    const bool live = tid < WIN_COLS;
+    int p = 0, slot = 0;
+    if (live) {
+        p = pos[((size_t)w * WIN_COLS + tid) * 2];
+        slot = pos[((size_t)w * WIN_COLS + tid) * 2 + 1];
+    }
+    const bool inside = live && p >= lo && p < hi && slot >= 0;
+    // the ops at the window's first and last position bracket every search
+    if (tid == 0 || tid == WIN_COLS - 1) {
+        const int e = tid == 0 ? 0 : 1;
+        s_p[e] = p;
+        s_op[e] = inside ? find_op(P, c0, c1 - 1, p) : (e ? c1 - 1 : c0);
+        if (!inside) s_p[e] = e ? hi : lo - 1;  // brackets nothing
+    }
+    __syncthreads();
+    uint32_t label = LABEL_GAP;
+    if (live && !inside)
+        __hip_atomic_fetch_or(err, LBL_ERR_RANGE, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT);
+    if (inside) {
+        // positions ascend inside a window; one that does not gets the
+        // whole alignment
+        const uint32_t olo = p >= s_p[0] && s_p[0] >= lo ? s_op[0] : c0;
+        const uint32_t ohi = p <= s_p[1] && s_p[1] < hi ? s_op[1] : c1 - 1;
+        const uint32_t j = find_op(P, olo, max(olo, ohi), p);
+        const uint32_t cw = P.cigar[j];
+        const uint32_t op = cw & 15u;
+        const int len = (int)(cw >> 4);
+        const int rp = P.op_rpos[j];
+        if (slot == 0) {
+            if (op_is_match(op))
+                label = read_base(P, r, P.op_qpos[j] + p - rp);
+            else if (op != OP_D && op != OP_N)  // no aligned op covers p
+                __hip_atomic_fetch_or(err, LBL_ERR_RANGE, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
+        } else if (p == rp + len - 1) {
+            // the slot-th base of the run of I ops behind the op's last
+            // position, whatever the op (M/=/X, D or N)
+            int need = slot;
+            for (uint32_t k = j + 1; k < c1; ++k) {
+                const uint32_t nx = P.cigar[k];
+                if ((nx & 15u) != OP_I) break;
+                const int l = (int)(nx >> 4);
+                if (need <= l) {
+                    label = read_base(P, r, P.op_qpos[k] + need - 1);
+                    break;
+                }
+                need -= l;
+            }
+        }
+    }
+    if (live) labels[(size_t)w * WIN_COLS + tid] = (uint8_t)label;
+    const int unknown = __syncthreads_or(live && label == LABEL_UNKNOWN);
+    if (tid == 0) keep[w] = unknown ? 0 : 1;
+}
+
+void truth_scan(const int32_t* ref_start, const int32_t* ref_end,
+                const uint32_t* cigar_off, const uint32_t* seq_off,
+                const uint32_t* cigar, const uint8_t* seq4, int32_t* op_rpos,
+                int32_t* op_qpos, int n, int32_t* err, hipStream_t stream) {
+    if (n <= 0) return;
+    const WinPack P = make_pack(ref_start, ref_end, nullptr, cigar_off,
+                                seq_off, cigar, seq4, op_rpos, op_qpos, n, 0,
+                                0);
+    hipLaunchKernelGGL(truth_scan_kernel, dim3((n + 3) / 4), dim3(256), 0,
+                       stream, P, err);
+}
+
+// `err` (one word) comes in zeroed; 0 <= index < n.
+void label_windows(const int32_t* ref_start, const int32_t* ref_end,
+                   const uint32_t* cigar_off, const uint32_t* seq_off,
+                   const uint32_t* cigar, const uint8_t* seq4,
+                   int32_t* op_rpos, int32_t* op_qpos, int n, int index,
+                   int lo, int hi, const int32_t* pos, int n_windows,
+                   uint8_t* labels, uint8_t* keep, int32_t* err,
+                   hipStream_t stream) {
+    if (n_windows <= 0) return;
+    const WinPack P = make_pack(ref_start, ref_end, nullptr, cigar_off,
+                                seq_off, cigar, seq4, op_rpos, op_qpos, n, 0,
+                                0);
+    hipLaunchKernelGGL(label_windows_kernel, dim3(n_windows), dim3(128), 0,
+                       stream, P, pos, index, lo, hi, labels, keep, err);
 }
 
 }  // namespace rk
