@@ -75,6 +75,17 @@ void xg_gemm2(const void* A, const void* Bt, const void* bias, void* C,
 void xg_gemm3(const void* A, int lda, const void* Bt, const void* bias,
               void* C, int M, int KP, hipStream_t stream);
 int xg_gemm3_tile_m();
+void xg_gemm3_stamped(const void* A, int lda, const void* Bt,
+                      const void* bias, void* C, int M, int KP,
+                      unsigned long long* stamps, hipStream_t stream);
+int xg_gemm3_stamp_words();
+void xg_gemm4(const void* A, int lda, const void* Bt, const void* bias,
+              void* C, int M, int KP, int max_wgs, hipStream_t stream);
+void xg_gemm4w(const void* A, int lda, const void* Bt, const void* bias,
+               void* C, int M, int max_wgs, hipStream_t stream);
+int xg_gemm4w_tile_m();
+bool xg_gemm4w_pays(int M);
+int xg_gemm4_cus();
 int atb_splitk_nslices(int K);
 void atb_splitk(const void* A, const void* B, float* ws, float* C, int M,
                 int N, int K, hipStream_t stream);
@@ -552,16 +563,20 @@ torch::Tensor xg_gemm2(torch::Tensor A, torch::Tensor Bt, torch::Tensor bias,
 // xg projection at the coalesced serving width (docs/KERNELS.md lesson 21):
 // A (M, 256|512) bf16, rows 16-B aligned with any leading dimension (a
 // column slice of a wider buffer is fine) x Bt (768, KP) + bias -> (M, 768).
-// Byte-identical to xg_gemm2 on the same values.
-torch::Tensor xg_gemm3(torch::Tensor A, torch::Tensor Bt, torch::Tensor bias,
-                       c10::optional<torch::Tensor> out_) {
+// Byte-identical to xg_gemm2 on the same values. This is the argument
+// contract xg_gemm3 and xg_gemm4 share; it returns the output tensor.
+static torch::Tensor xg3_contract(const torch::Tensor& A,
+                                  const torch::Tensor& Bt,
+                                  const torch::Tensor& bias,
+                                  c10::optional<torch::Tensor> out_,
+                                  int64_t& lda) {
     check(Bt, torch::kBFloat16, "Bt");
     check(bias, torch::kBFloat16, "bias");
     TORCH_CHECK(A.is_cuda() && A.scalar_type() == torch::kBFloat16 &&
                     A.dim() == 2, "A must be a 2-D bf16 GPU tensor");
     const int64_t M = A.size(0), KP = A.size(1);
     TORCH_CHECK(KP == 256 || KP == 512, "A must be (M, 256|512)");
-    const int64_t lda = M > 1 ? A.stride(0) : KP;
+    lda = M > 1 ? A.stride(0) : KP;
     TORCH_CHECK(A.stride(1) == 1 && lda >= KP && lda % 8 == 0 &&
                     reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0,
                 "A rows must be unit-stride and 16-byte aligned");
@@ -578,9 +593,64 @@ torch::Tensor xg_gemm3(torch::Tensor A, torch::Tensor Bt, torch::Tensor bias,
     } else {
         C = torch::empty({M, 768}, A.options());
     }
-    rk::xg_gemm3(A.data_ptr(), (int)lda, Bt.data_ptr(), bias.data_ptr(),
-                 C.data_ptr(), (int)M, (int)KP, cur_stream());
     return C;
+}
+
+torch::Tensor xg_gemm3(torch::Tensor A, torch::Tensor Bt, torch::Tensor bias,
+                       c10::optional<torch::Tensor> out_) {
+    int64_t lda = 0;
+    torch::Tensor C = xg3_contract(A, Bt, bias, out_, lda);
+    rk::xg_gemm3(A.data_ptr(), (int)lda, Bt.data_ptr(), bias.data_ptr(),
+                 C.data_ptr(), (int)A.size(0), (int)A.size(1), cur_stream());
+    return C;
+}
+
+// xg_gemm3's successors (docs/KERNELS.md lesson 24): same contract,
+// byte-identical output. form "stream" is the persistent tile stream (both
+// K), "wstat" the W-stationary kernel (K = 256 and M % 256 == 0 only);
+// "auto" takes wstat where it applies, else stream. max_wgs > 0 caps the
+// grid; 0 is each form's default.
+static bool xg4w_applies(int64_t M, int64_t KP) {
+    return KP == 256 && M % rk::xg_gemm4w_tile_m() == 0;
+}
+
+torch::Tensor xg_gemm4(torch::Tensor A, torch::Tensor Bt, torch::Tensor bias,
+                       c10::optional<torch::Tensor> out_, int64_t max_wgs,
+                       const std::string& form) {
+    int64_t lda = 0;
+    torch::Tensor C = xg3_contract(A, Bt, bias, out_, lda);
+    const int64_t M = A.size(0), KP = A.size(1);
+    TORCH_CHECK(max_wgs >= 0 && max_wgs <= (1 << 20), "max_wgs out of range");
+    TORCH_CHECK(form == "auto" || form == "stream" || form == "wstat",
+                "form must be auto, stream or wstat");
+    TORCH_CHECK(form != "wstat" || xg4w_applies(M, KP),
+                "form wstat needs K = 256 and M % 256 == 0");
+    if (form == "wstat" || (form == "auto" && xg4w_applies(M, KP)))
+        rk::xg_gemm4w(A.data_ptr(), (int)lda, Bt.data_ptr(), bias.data_ptr(),
+                      C.data_ptr(), (int)M, (int)max_wgs, cur_stream());
+    else
+        rk::xg_gemm4(A.data_ptr(), (int)lda, Bt.data_ptr(), bias.data_ptr(),
+                     C.data_ptr(), (int)M, (int)KP, (int)max_wgs,
+                     cur_stream());
+    return C;
+}
+
+// The timing-only instantiation of xg_gemm3 (scripts/xg4_phases.py):
+// returns (out, stamps) with stamps (workgroups, xg_gemm3_stamp_words) i64.
+std::tuple<torch::Tensor, torch::Tensor> xg_gemm3_phases(
+    torch::Tensor A, torch::Tensor Bt, torch::Tensor bias) {
+    int64_t lda = 0;
+    torch::Tensor C = xg3_contract(A, Bt, bias, c10::nullopt, lda);
+    const int64_t nwg = A.size(0) / rk::xg_gemm3_tile_m() * 6;
+    torch::Tensor stamps = torch::zeros(
+        {nwg, (int64_t)rk::xg_gemm3_stamp_words()},
+        A.options().dtype(torch::kInt64));
+    rk::xg_gemm3_stamped(
+        A.data_ptr(), (int)lda, Bt.data_ptr(), bias.data_ptr(), C.data_ptr(),
+        (int)A.size(0), (int)A.size(1),
+        reinterpret_cast<unsigned long long*>(stamps.data_ptr<int64_t>()),
+        cur_stream());
+    return {C, stamps};
 }
 
 // GRU layer weight gradients in ONE binding call: dU (both dirs, via
@@ -1136,6 +1206,19 @@ struct ServeSlot {
         const char* f = getenv("ROKO_XG3");
         return !(f && std::string(f) == "0");
     }();
+    // xg_gemm3's successors (lesson 24) on the xg3 path, selected per K.
+    // Shipped: the W-stationary kernel for the K = 256 layers of slots wide
+    // enough for it to pay (set in ctor), xg_gemm3 for layer 0 and for
+    // narrower slots. ROKO_XG4=0 keeps xg_gemm3 everywhere; ROKO_XG4=wstat
+    // takes the W-stationary kernel at every width it can run;
+    // ROKO_XG4=stream takes the persistent tile stream for both K (the
+    // measured negative, kept as the A/B partner).
+    bool use_xg4 = [] {
+        const char* f = getenv("ROKO_XG4");
+        return !(f && std::string(f) == "0");
+    }();
+    // per layer family: 0 xg_gemm3, 1 stream, 2 W-stationary
+    int xg4_k256 = 2, xg4_k512 = 0;
     bool use_gslot = false;
     bool xg2_path = false;   // set in ctor: raw (capture-legal) layer path
     bool xg3_path = false;   // set in ctor: xg2_path taken with xg_gemm3
@@ -1190,6 +1273,23 @@ struct ServeSlot {
                    w_ih_p[0].size(1) == 512 && w_ih_p[1].size(1) == 256 &&
                    w_ih_p[2].size(1) == 256;
         seq_ld = xg3_path ? 512 : 500;
+        bool force_wstat = false;
+        if (const char* f = getenv("ROKO_XG4")) {
+            if (std::string(f) == "stream") xg4_k256 = xg4_k512 = 1;
+            force_wstat = std::string(f) == "wstat";
+        }
+        if (!use_xg4 || !xg3_path) xg4_k256 = xg4_k512 = 0;
+        // W-stationary tiles are 256 rows, and with one walker per 1/40 of
+        // the m-tiles the kernel wins only where a walker has many rounds:
+        // measured 1.09x at M = 92,160 (9 rounds) and 0.87x at 11,520 (45
+        // m-tiles on 40 walkers). Narrower slots keep xg_gemm3 unless
+        // ROKO_XG4=wstat forces it wherever it applies.
+        if (xg4_k256 == 2 && !(force_wstat ? (90 * B_) % rk::xg_gemm4w_tile_m() == 0
+                                           : rk::xg_gemm4w_pays(90 * B_)))
+            xg4_k256 = 0;
+        // the grid size comes from a device query: make it here, not under
+        // stream capture
+        if (xg4_k256 || xg4_k512) (void)rk::xg_gemm4_cus();
         if (const char* f = getenv("ROKO_GSLOT"))
             use_gslot = std::string(f) == "1";
         else
@@ -1264,7 +1364,17 @@ struct ServeSlot {
             }
         } else {
             for (int l = 0; l < 3; ++l) {
-                if (xg3_path)
+                const int xg4_form = l == 0 ? xg4_k512 : xg4_k256;
+                if (xg4_form == 2)
+                    rk::xg_gemm4w(hseq.data_ptr(), 256, w_ih_p[l].data_ptr(),
+                                  b_ih[l].data_ptr(), xg.data_ptr(), 90 * B,
+                                  0, s);
+                else if (xg4_form == 1)
+                    rk::xg_gemm4((l == 0 ? seq : hseq).data_ptr(),
+                                 l == 0 ? 512 : 256, w_ih_p[l].data_ptr(),
+                                 b_ih[l].data_ptr(), xg.data_ptr(), 90 * B,
+                                 l == 0 ? 512 : 256, 0, s);
+                else if (xg3_path)
                     rk::xg_gemm3((l == 0 ? seq : hseq).data_ptr(),
                                  l == 0 ? 512 : 256, w_ih_p[l].data_ptr(),
                                  b_ih[l].data_ptr(), xg.data_ptr(), 90 * B,
@@ -1629,6 +1739,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("timing") = py::none());
     m.def("xg_gemm3", &xg_gemm3, py::arg("A"), py::arg("Bt"), py::arg("bias"),
           py::arg("out") = py::none());
+    m.def("xg_gemm4", &xg_gemm4, py::arg("A"), py::arg("Bt"), py::arg("bias"),
+          py::arg("out") = py::none(), py::arg("max_wgs") = 0,
+          py::arg("form") = "auto");
+    m.def("xg_gemm4_cus", [] { return rk::xg_gemm4_cus(); });
+    m.def("xg_gemm3_phases", &xg_gemm3_phases, py::arg("A"), py::arg("Bt"),
+          py::arg("bias"));
     m.def("front_de_timed", &front_de_timed, py::arg("ids"), py::arg("dt1g"),
           py::arg("w1"), py::arg("seed"), py::arg("keep"), py::arg("dbg") = 0);
     m.def("front_bwd", &front_bwd, py::arg("ids"), py::arg("dseq"),

@@ -648,16 +648,49 @@ RK_DEV int swz(int row, int q) {
     return row * 128 + ((q ^ ((row >> 1) & 7)) << 4);
 }
 
-template <int KP>
+// Phase stamps, STAMP instantiations only (scripts/xg4_phases.py): the
+// shader clock as one statement with its own lgkmcnt(0), fenced so nothing
+// moves across it. A stamped build forbids overlaps the real kernel has:
+// read its shares, never its length.
+constexpr int STAMP_WORDS = 16;  // u64 per workgroup, layout in xg4_phases.py
+RK_DEV unsigned long long stamp_clock() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+RK_DEV unsigned long long stamp_realtime() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+// (XCC id << 32) | HW_ID: which CU of which XCD this workgroup ran on
+RK_DEV unsigned long long stamp_place() {
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\t"
+                 "s_getreg_b32 %1, hwreg(HW_REG_XCC_ID)"
+                 : "=s"(hw), "=s"(xcc));
+    return ((unsigned long long)xcc << 32) | hw;
+}
+
+template <int KP, bool STAMP = false>
 __global__ __launch_bounds__(WAVES * 64, 2) void xg_gemm3_kernel(
     const bf16* __restrict__ A,     // (M, KP) rows strided by lda (16-B rows)
     const bf16* __restrict__ Bt,    // (768, KP) row-major = B^T, zero-padded
     const bf16* __restrict__ bias,  // (768)
     bf16* __restrict__ C,           // (M, 768)
-    int lda, int nwg) {
+    int lda, int nwg, unsigned long long* __restrict__ stamps = nullptr) {
     constexpr int KB = KP / BK;
     // [buf][A | B][16 KB]; the epilogue reuses it as 4 x 8 KB wave images
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * 2 * TILE_BYTES];
+    unsigned long long ts[KB + 3] = {}, rt0 = 0;
+    if constexpr (STAMP) {
+        rt0 = stamp_realtime();
+        ts[0] = stamp_clock();
+    }
 
     const int tid = threadIdx.x;
     const int wid = tid >> 6;
@@ -743,6 +776,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void xg_gemm3_kernel(
     if (KB > 1) issue(1, ra[1], rb[1]);
     commit(0, ra[0], rb[0]);
     __syncthreads();
+    if constexpr (STAMP) ts[1] = stamp_clock();
 #pragma unroll
     for (int kq = 0; kq < KB; ++kq) {
         if (kq + 2 < KB) issue(kq + 2, ra[kq & 1], rb[kq & 1]);
@@ -750,6 +784,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void xg_gemm3_kernel(
         if (kq + 1 < KB) commit((kq + 1) & 1, ra[(kq + 1) & 1],
                                 rb[(kq + 1) & 1]);
         __syncthreads();
+        if constexpr (STAMP) ts[2 + kq] = stamp_clock();
     }
 
     // epilogue: fp32 bias add, one bf16 round, 8-B packed writes into this
@@ -787,6 +822,24 @@ __global__ __launch_bounds__(WAVES * 64, 2) void xg_gemm3_kernel(
                     img + row * 128 + ((j ^ (row & 7)) << 4));
         }
     }
+    if constexpr (STAMP) {
+        // [0] entry, [1] first barrier, [2 .. 2+KB) end of each slice (the
+        // last one is the epilogue's start), [10] last store issued, [11]/[12]
+        // wall clock at entry / exit, [13] placement. Lane 0 of wave 0
+        // writes them, to a buffer nothing else in the kernel touches.
+        ts[KB + 2] = stamp_clock();
+        const unsigned long long rt1 = stamp_realtime();
+        const unsigned long long place = stamp_place();
+        if (tid == 0) {
+            unsigned long long* o = stamps + (size_t)orig * STAMP_WORDS;
+#pragma unroll
+            for (int i = 0; i < KB + 2; ++i) o[i] = ts[i];
+            o[10] = ts[KB + 2];
+            o[11] = rt0;
+            o[12] = rt1;
+            o[13] = place;
+        }
+    }
 }
 
 }  // namespace xg3
@@ -802,16 +855,516 @@ void xg_gemm3(const void* A, int lda, const void* Bt, const void* bias,
                            static_cast<const bf16*>(A),
                            static_cast<const bf16*>(Bt),
                            static_cast<const bf16*>(bias),
-                           static_cast<bf16*>(C), lda, nwg);
+                           static_cast<bf16*>(C), lda, nwg, nullptr);
     else if (KP == 256)
         hipLaunchKernelGGL((xg3::xg_gemm3_kernel<256>), grid, block, 0, stream,
                            static_cast<const bf16*>(A),
                            static_cast<const bf16*>(Bt),
                            static_cast<const bf16*>(bias),
-                           static_cast<bf16*>(C), lda, nwg);
+                           static_cast<bf16*>(C), lda, nwg, nullptr);
 }
 
 int xg_gemm3_tile_m() { return xg3::BM; }
+
+// The timing-only instantiation of xg_gemm3 (scripts/xg4_phases.py): same
+// grid, same output, plus STAMP_WORDS u64 per workgroup in `stamps`.
+void xg_gemm3_stamped(const void* A, int lda, const void* Bt,
+                      const void* bias, void* C, int M, int KP,
+                      unsigned long long* stamps, hipStream_t stream) {
+    const int nwg = (M / xg3::BM) * xg3::NT;
+    dim3 grid(nwg), block(xg3::WAVES * 64);
+    if (KP == 512)
+        hipLaunchKernelGGL((xg3::xg_gemm3_kernel<512, true>), grid, block, 0,
+                           stream, static_cast<const bf16*>(A),
+                           static_cast<const bf16*>(Bt),
+                           static_cast<const bf16*>(bias),
+                           static_cast<bf16*>(C), lda, nwg, stamps);
+    else if (KP == 256)
+        hipLaunchKernelGGL((xg3::xg_gemm3_kernel<256, true>), grid, block, 0,
+                           stream, static_cast<const bf16*>(A),
+                           static_cast<const bf16*>(Bt),
+                           static_cast<const bf16*>(bias),
+                           static_cast<bf16*>(C), lda, nwg, stamps);
+}
+
+int xg_gemm3_stamp_words() { return xg3::STAMP_WORDS; }
+
+// ---------------------------------------------------------------------------
+// xg_gemm4: xg_gemm3 as a persistent tile stream (docs/KERNELS.md lesson 24).
+// Tile, waves, swizzled LDS image, fragment reads, MFMA order, bias add and
+// rounding are xg_gemm3's, so the output equals it byte for byte. What
+// changed is everything BETWEEN tiles: min(tiles, 2 x CUs) workgroups each
+// walk their share of the tiles (n fastest; an XCD's workgroups hold one
+// contiguous range and stride through it together, so an m-tile's six
+// n-tiles still meet in one L2), and the k-slices of a workgroup's whole
+// walk form ONE stream: slice s + 2 is issued
+// before burst s and slice s + 1 committed after it whether or not a tile
+// ends in between. The next tile's first two slices are in flight under
+// this tile's last two bursts and its epilogue; the prologue's exposed load
+// latency is paid once per workgroup instead of once per tile.
+//
+// Tile boundary. KB is even: a tile's last slice is read from buffer 1 and
+// the next tile's slice 0 is committed to buffer 0 in the usual place. The
+// epilogue's four 8 KB wave images therefore live in buffer 1 only:
+//   barrier (end of the last slice: every wave is done reading buffer 1)
+//   -> each wave writes and reads back ITS OWN image (LDS operations of one
+//      wave execute in order; no other wave touches that image)
+//   -> barrier (every image read has landed)
+//   -> next tile: burst 0 from buffer 0, then commit of slice 1 INTO buffer 1.
+// The bias values are loaded at the head of the tile, not in the epilogue,
+// where the load would queue behind two slices of staged loads.
+namespace xg4 {
+
+using xg3::BK;
+using xg3::BM;
+using xg3::BN;
+using xg3::NT;
+using xg3::TILE_BYTES;
+using xg3::WAVES;
+using xg3::XN;
+using xg3::swz;
+
+template <int KP>
+__global__ __launch_bounds__(WAVES * 64, 2) void xg_gemm4_kernel(
+    const bf16* __restrict__ A,     // (M, KP) rows strided by lda (16-B rows)
+    const bf16* __restrict__ Bt,    // (768, KP) row-major = B^T, zero-padded
+    const bf16* __restrict__ bias,  // (768)
+    bf16* __restrict__ C,           // (M, 768)
+    int lda, int tq, int tr) {      // tiles / grid, tiles % grid
+    constexpr int KB = KP / BK;
+    static_assert(KB >= 2 && KB % 2 == 0, "a tile must end in buffer 1");
+    // [buf][A | B][16 KB]; buffer 1 doubles as the 4 x 8 KB wave images
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * 2 * TILE_BYTES];
+
+    const int tid = threadIdx.x;
+    const int wid = tid >> 6;
+    const int lane = tid & 63;
+    const int lrow = lane >> 4;
+    const int lcol = lane & 15;
+    const int wm = wid >> 1, wn = wid & 1;
+
+    // xg_gemm3's bijective XCD remap over the persistent grid: workgroups
+    // that share blockIdx % 8 share an XCD and are numbered w0 .. w0 + gx - 1.
+    // Balanced runs (the first tr workgroups tq + 1 tiles, the rest tq) give
+    // that XCD the contiguous tile range [ta, tb); inside it workgroup j
+    // takes every gx-th tile from ta + j. At any moment the XCD's workgroups
+    // are therefore on ~gx CONSECUTIVE tiles, as under xg_gemm3's dispatch
+    // order: an m-tile's six n-tiles run side by side in one L2. (One
+    // contiguous run per workgroup puts gx different m-tiles in flight per
+    // XCD, 64 x 64 KB against 4 MB of L2, and measured 1.28x SLOWER than
+    // xg_gemm3 at M = 92,160.)
+    const int nwg = gridDim.x;
+    const int orig = blockIdx.x;
+    const int xcd = orig & 7;
+    const int q8 = nwg >> 3, r8 = nwg & 7;
+    const int w0 = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+    const int gx = q8 + (xcd < r8 ? 1 : 0);
+    const int ta = w0 * tq + (w0 < tr ? w0 : tr);
+    const int tb = (w0 + gx) * tq + (w0 + gx < tr ? w0 + gx : tr);
+    const int t0 = ta + (orig >> 3);
+    if (t0 >= tb) return;  // a spare workgroup touches nothing
+
+    f32x4 acc[4][4];
+    bf16x8 ra[2][4], rb[2][4];
+    const int s_row = tid >> 3, s_q = tid & 7;
+    const int s_off = swz(s_row, s_q);
+    auto a_of = [&](int t) {
+        return A + (size_t)((t / NT) * BM + s_row) * lda + s_q * 8;
+    };
+    auto b_of = [&](int t) {
+        return Bt + (size_t)((t % NT) * BN + s_row) * KP + s_q * 8;
+    };
+    auto issue = [&](const bf16* a_src, const bf16* b_src, int kq,
+                     bf16x8(&va)[4], bf16x8(&vb)[4]) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            va[p] = *reinterpret_cast<const bf16x8*>(
+                a_src + (size_t)p * 32 * lda + kq * BK);
+            vb[p] = *reinterpret_cast<const bf16x8*>(
+                b_src + (size_t)p * 32 * KP + kq * BK);
+        }
+    };
+    auto commit = [&](int buf, bf16x8(&va)[4], bf16x8(&vb)[4]) {
+        unsigned char* ab = lds + buf * 2 * TILE_BYTES;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            *reinterpret_cast<bf16x8*>(ab + p * 32 * 128 + s_off) = va[p];
+            *reinterpret_cast<bf16x8*>(ab + TILE_BYTES + p * 32 * 128 + s_off) =
+                vb[p];
+        }
+    };
+    const int fsw = (lcol >> 1) & 7;
+    const int fa_off = (wm * 64 + lcol) * 128;
+    const int fb_off = TILE_BYTES + (wn * 64 + lcol) * 128;
+    auto mfma_step = [&](int buf) {
+        const unsigned char* ab = lds + buf * 2 * TILE_BYTES;
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh) {
+            const int ch = ((kh * 4 + lrow) ^ fsw) << 4;
+            bf16x8 af[4], wf[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                af[t] = *reinterpret_cast<const bf16x8*>(
+                    ab + fa_off + t * 16 * 128 + ch);
+                wf[t] = *reinterpret_cast<const bf16x8*>(
+                    ab + fb_off + t * 16 * 128 + ch);
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt)
+                    acc[mt][nt] = mfma16x16x32(wf[nt], af[mt], acc[mt][nt]);
+        }
+    };
+
+    // One tile of the walk. On entry slice 0 is in buffer 0 (committed and
+    // barriered) and slice 1 is in flight in set 1; on exit the same holds
+    // for tile `nxt`. The last tile of a run names itself as `nxt`: its
+    // look-ahead loads re-read valid lines of its own tile and are never
+    // used, which keeps every load of the stream out of a branch.
+    unsigned char* img = lds + 2 * TILE_BYTES + wid * (64 * 128);
+    const int r8l = lane >> 3, j8 = lane & 7;
+    auto tile = [&](int t, int nxt) {
+        const int m0 = (t / NT) * BM, n0 = (t % NT) * BN;
+        const bf16* a_cur = a_of(t);
+        const bf16* b_cur = b_of(t);
+        const bf16* a_nxt = a_of(nxt);
+        const bf16* b_nxt = b_of(nxt);
+        bf16x4 bv[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+            bv[nt] = *reinterpret_cast<const bf16x4*>(
+                reinterpret_cast<const __bf16*>(bias) + n0 + wn * 64 + nt * 16 +
+                lrow * 4);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+                acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kq = 0; kq < KB; ++kq) {
+            if (kq + 2 < KB)
+                issue(a_cur, b_cur, kq + 2, ra[kq & 1], rb[kq & 1]);
+            else
+                issue(a_nxt, b_nxt, kq + 2 - KB, ra[kq & 1], rb[kq & 1]);
+            // pin the loads ahead of the burst: left alone, the scheduler
+            // sinks a tile's last look-ahead below the epilogue and the
+            // next tile opens on vmcnt(0) (lesson 23 again)
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_step(kq & 1);
+            commit((kq + 1) & 1, ra[(kq + 1) & 1], rb[(kq + 1) & 1]);
+            __syncthreads();
+        }
+        // epilogue: xg_gemm3's, through this wave's image in buffer 1
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const int nl = nt * 16 + lrow * 4;
+            float br[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) br[i] = (float)bv[nt][i];
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const int row = mt * 16 + lcol;
+                alignas(8) bf16 o[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] = f2bf(acc[mt][nt][i] + br[i]);
+                *reinterpret_cast<uint64_t*>(
+                    img + row * 128 + (((nl >> 3) ^ (row & 7)) << 4) +
+                    (nl & 4) * 2) = *reinterpret_cast<const uint64_t*>(o);
+            }
+        }
+        bf16* cdst = C + (size_t)(m0 + wm * 64 + r8l) * XN + n0 + wn * 64 + j8 * 8;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const int row = p * 8 + r8l;
+            *reinterpret_cast<bf16x8*>(cdst + (size_t)p * 8 * XN) =
+                *reinterpret_cast<const bf16x8*>(
+                    img + row * 128 + ((j8 ^ (row & 7)) << 4));
+        }
+        __syncthreads();  // image reads landed before slice 1 enters buffer 1
+    };
+
+    // the walk's only full drain: slice 0 of the first tile
+    issue(a_of(t0), b_of(t0), 0, ra[0], rb[0]);
+    issue(a_of(t0), b_of(t0), 1, ra[1], rb[1]);
+    commit(0, ra[0], rb[0]);
+    __syncthreads();
+    // One loop, first tile included. (Peeling the first tile lets the loop
+    // count the previous epilogue's stores, vmcnt(27..20) instead of
+    // (19..12) at a tile's first commit; it measured 1-3% SLOWER.)
+    for (int t = t0; t < tb; t += gx) tile(t, t + gx < tb ? t + gx : t);
+}
+
+}  // namespace xg4
+
+// ---------------------------------------------------------------------------
+// xg_gemm4w: the K = 256 projections with W STATIONARY (lesson 24). The stamps
+// of xg_gemm3 and the stream form above agree that these kernels are bound by
+// what a CU can pull out of L2, not by what is serial in a tile: so fetch
+// less. One 512-thread workgroup per CU (8 waves, 4 (m) x 2 (n), 64 x 64
+// each) is bound to ONE 128-column n-tile, loads that tile's W (128 x 256
+// bf16, 64 KB) into LDS once, and then streams 256-row A slices through two
+// 32 KB buffers with the cross-tile slice stream of xg_gemm4: no B staging
+// at all, global fetch per output halved, LDS array work per MFMA cycle
+// 0.75 of xg_gemm3's. Arithmetic, fragment layout and rounding are
+// xg_gemm3's: the output equals it byte for byte.
+//
+// Placement. The grid is 6 x G workgroups, G "walkers" of m-tiles per
+// n-tile. With G a multiple of 8, workgroup b runs on XCD b % 8; that XCD
+// gets a contiguous eighth of the m-tiles and G / 8 walkers per n-tile, and
+// its six workgroups of one walker are on the SAME m-tile at the same time:
+// the A tile leaves HBM once and is read six times from that XCD's L2.
+// Default G = 8 x (CUs per XCD / 6) = 40: 240 of 256 CUs, 9 exact rounds at
+// M = 92,160 (16 CUs idle buys zero tail). Any other G (tests) walks
+// m = g, g + G, ... with no XCD structure.
+//
+// Epilogue. A tile ends in A buffer 1 (KB = 4); buffer 0 is already being
+// filled with the next tile's slice 0. Eight 8 KB images do not fit in one
+// 32 KB buffer, so each wave goes through a 4 KB image twice (32 rows each).
+// The image is wave-private and one wave's LDS operations execute in order,
+// so neither the write -> read nor the read -> rewrite needs a barrier; one
+// barrier after the last read precedes the commit of slice 1 into buffer 1.
+namespace xg4w {
+
+using xg3::BK;
+using xg3::BN;
+using xg3::NT;
+using xg3::TILE_BYTES;
+using xg3::XN;
+using xg3::swz;
+
+constexpr int KP = 256;
+constexpr int KB = KP / BK;             // 4: even, a tile ends in buffer 1
+constexpr int BMW = 256;                // C rows per tile
+constexpr int WAVES = 8;                // 4 (m) x 2 (n)
+constexpr int A_BYTES = BMW * BK * 2;   // one A slice: 32 KB
+constexpr int W_BYTES = KB * TILE_BYTES;  // the W tile, [kq][128 rows][128 B]
+
+__global__ __launch_bounds__(WAVES * 64, 2) void xg_gemm4w_kernel(
+    const bf16* __restrict__ A,     // (M, 256) rows strided by lda (16-B rows)
+    const bf16* __restrict__ Bt,    // (768, 256) row-major = B^T
+    const bf16* __restrict__ bias,  // (768)
+    bf16* __restrict__ C,           // (M, 768)
+    int lda, int mtiles, int groups) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[W_BYTES + 2 * A_BYTES];
+    unsigned char* abuf = lds + W_BYTES;
+
+    const int tid = threadIdx.x;
+    const int wid = tid >> 6;
+    const int lane = tid & 63;
+    const int lrow = lane >> 4;
+    const int lcol = lane & 15;
+    const int wm = wid >> 1, wn = wid & 1;
+
+    const int b = blockIdx.x;
+    int n_t, m_first, m_step, m_end;
+    if ((groups & 7) == 0) {
+        const int xcd = b & 7, j = b >> 3;
+        const int q = mtiles >> 3, r = mtiles & 7;
+        const int ta = xcd * q + (xcd < r ? xcd : r);
+        n_t = j % NT;
+        m_step = groups >> 3;
+        m_first = ta + j / NT;
+        m_end = ta + q + (xcd < r ? 1 : 0);
+    } else {
+        n_t = b % NT;
+        m_step = groups;
+        m_first = b / NT;
+        m_end = mtiles;
+    }
+    if (m_first >= m_end) return;  // a spare workgroup touches nothing
+    const int n0 = n_t * BN;
+
+    // W tile -> LDS, once: 32 lanes read one full 512-B row of Bt
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int row = (tid >> 5) + 16 * i, cc = tid & 31;
+        *reinterpret_cast<bf16x8*>(lds + (cc >> 3) * TILE_BYTES + swz(row, cc & 7)) =
+            *reinterpret_cast<const bf16x8*>(Bt + (size_t)(n0 + row) * KP + cc * 8);
+    }
+    bf16x4 bv[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+        bv[nt] = *reinterpret_cast<const bf16x4*>(
+            reinterpret_cast<const __bf16*>(bias) + n0 + wn * 64 + nt * 16 +
+            lrow * 4);
+
+    f32x4 acc[4][4];
+    bf16x8 ra[2][4];
+    const int s_row = tid >> 3, s_q = tid & 7;  // + p * 64 rows: same swizzle
+    const int s_off = swz(s_row, s_q);
+    auto a_of = [&](int m) {
+        return A + (size_t)(m * BMW + s_row) * lda + s_q * 8;
+    };
+    auto issue = [&](const bf16* a_src, int kq, bf16x8(&va)[4]) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            va[p] = *reinterpret_cast<const bf16x8*>(
+                a_src + (size_t)p * 64 * lda + kq * BK);
+    };
+    auto commit = [&](int buf, bf16x8(&va)[4]) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            *reinterpret_cast<bf16x8*>(abuf + buf * A_BYTES + p * 64 * 128 +
+                                       s_off) = va[p];
+    };
+    const int fsw = (lcol >> 1) & 7;
+    const int fa_off = (wm * 64 + lcol) * 128;
+    const int fb_off = (wn * 64 + lcol) * 128;
+    auto mfma_step = [&](int buf, int kq) {
+        const unsigned char* ab = abuf + buf * A_BYTES;
+        const unsigned char* wb = lds + kq * TILE_BYTES;
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh) {
+            const int ch = ((kh * 4 + lrow) ^ fsw) << 4;
+            bf16x8 af[4], wf[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                af[t] = *reinterpret_cast<const bf16x8*>(
+                    ab + fa_off + t * 16 * 128 + ch);
+                wf[t] = *reinterpret_cast<const bf16x8*>(
+                    wb + fb_off + t * 16 * 128 + ch);
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt)
+                    acc[mt][nt] = mfma16x16x32(wf[nt], af[mt], acc[mt][nt]);
+        }
+    };
+
+    unsigned char* img = abuf + A_BYTES + wid * (32 * 128);
+    const int r8l = lane >> 3, j8 = lane & 7;
+    // as xg_gemm4's tile: slice 0 committed and slice 1 in flight on entry,
+    // the same for m-tile `nxt` on exit; the last tile names itself
+    auto tile = [&](int m, int nxt) {
+        const bf16* a_cur = a_of(m);
+        const bf16* a_nxt = a_of(nxt);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+                acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kq = 0; kq < KB; ++kq) {
+            if (kq + 2 < KB)
+                issue(a_cur, kq + 2, ra[kq & 1]);
+            else
+                issue(a_nxt, kq + 2 - KB, ra[kq & 1]);
+            __builtin_amdgcn_sched_barrier(0);  // loads stay ahead of the burst
+            mfma_step(kq & 1, kq);
+            commit((kq + 1) & 1, ra[(kq + 1) & 1]);
+            __syncthreads();
+        }
+        bf16* cdst = C + (size_t)(m * BMW + wm * 64 + r8l) * XN + n0 +
+                     wn * 64 + j8 * 8;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const int nl = nt * 16 + lrow * 4;
+                float br[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) br[i] = (float)bv[nt][i];
+#pragma unroll
+                for (int mh = 0; mh < 2; ++mh) {
+                    const int row = mh * 16 + lcol;
+                    alignas(8) bf16 o[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        o[i] = f2bf(acc[h * 2 + mh][nt][i] + br[i]);
+                    *reinterpret_cast<uint64_t*>(
+                        img + row * 128 + (((nl >> 3) ^ (row & 7)) << 4) +
+                        (nl & 4) * 2) = *reinterpret_cast<const uint64_t*>(o);
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int row = p * 8 + r8l;
+                *reinterpret_cast<bf16x8*>(cdst + (size_t)(h * 32 + p * 8) * XN) =
+                    *reinterpret_cast<const bf16x8*>(
+                        img + row * 128 + ((j8 ^ (row & 7)) << 4));
+            }
+        }
+        __syncthreads();  // image reads landed before slice 1 enters buffer 1
+    };
+
+    issue(a_of(m_first), 0, ra[0]);
+    issue(a_of(m_first), 1, ra[1]);
+    commit(0, ra[0]);
+    __syncthreads();  // also publishes the W tile
+    for (int m = m_first; m < m_end; m += m_step)
+        tile(m, m + m_step < m_end ? m + m_step : m);
+}
+
+}  // namespace xg4w
+
+static int xg4_cus_cached = 0;
+
+// CU count of the current device, queried once (never under stream capture:
+// ServeSlot asks for it when a slot is built)
+int xg_gemm4_cus() {
+    if (xg4_cus_cached == 0) {
+        int dev = 0, cus = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                    dev);
+        xg4_cus_cached = cus > 0 ? cus : 256;
+    }
+    return xg4_cus_cached;
+}
+
+// Same contract as xg_gemm3. max_wgs > 0 caps the grid (tests force long
+// walks at small M with it); 0 is the default, 2 x CU count: the two
+// workgroups per CU that 64 KB of LDS and 2 waves per SIMD allow.
+void xg_gemm4(const void* A, int lda, const void* Bt, const void* bias,
+              void* C, int M, int KP, int max_wgs, hipStream_t stream) {
+    const int tiles = (M / xg4::BM) * xg4::NT;
+    const int cap = max_wgs > 0 ? max_wgs : 2 * xg_gemm4_cus();
+    const int nwg = tiles < cap ? tiles : cap;
+    dim3 grid(nwg), block(xg4::WAVES * 64);
+    if (KP == 512)
+        hipLaunchKernelGGL((xg4::xg_gemm4_kernel<512>), grid, block, 0, stream,
+                           static_cast<const bf16*>(A),
+                           static_cast<const bf16*>(Bt),
+                           static_cast<const bf16*>(bias),
+                           static_cast<bf16*>(C), lda, tiles / nwg, tiles % nwg);
+    else if (KP == 256)
+        hipLaunchKernelGGL((xg4::xg_gemm4_kernel<256>), grid, block, 0, stream,
+                           static_cast<const bf16*>(A),
+                           static_cast<const bf16*>(Bt),
+                           static_cast<const bf16*>(bias),
+                           static_cast<bf16*>(C), lda, tiles / nwg, tiles % nwg);
+}
+
+// The W-stationary form: KP = 256 and M % 256 == 0 only (the callers fall
+// back to xg_gemm3 otherwise). max_wgs > 0 caps the grid at 6 x
+// max(1, max_wgs / 6) workgroups; 0 is 6 x 8 x (CUs per XCD / 6).
+int xg_gemm4w_tile_m() { return xg4w::BMW; }
+
+static int xg4w_default_groups() {
+    const int g = 8 * (xg_gemm4_cus() / 8 / xg4w::NT);
+    return g > 0 ? g : 1;
+}
+
+// where the serving slots take this form: whole tiles and at least eight
+// rounds per walker (measured at nine; it loses at two)
+bool xg_gemm4w_pays(int M) {
+    return M % xg4w::BMW == 0 && M / xg4w::BMW >= 8 * xg4w_default_groups();
+}
+
+void xg_gemm4w(const void* A, int lda, const void* Bt, const void* bias,
+               void* C, int M, int max_wgs, hipStream_t stream) {
+    const int mtiles = M / xg4w::BMW;
+    int groups = max_wgs > 0 ? max_wgs / xg4w::NT : xg4w_default_groups();
+    if (groups < 1) groups = 1;
+    if (groups > mtiles) groups = mtiles;
+    hipLaunchKernelGGL(xg4w::xg_gemm4w_kernel, dim3(groups * xg4w::NT),
+                       dim3(xg4w::WAVES * 64), 0, stream,
+                       static_cast<const bf16*>(A), static_cast<const bf16*>(Bt),
+                       static_cast<const bf16*>(bias), static_cast<bf16*>(C),
+                       lda, mtiles, groups);
+}
 
 void xg_gemm(const void* A, const void* B, const void* bias, void* C, int M,
              int KP, hipStream_t stream) {
