@@ -128,6 +128,15 @@ class TrainConfig:
     resume: bool = False
     #: gradient-bucket size (bytes) for the RCCL all-reduce overlap
     bucket_bytes: int = 2 << 20
+    #: where batches are drawn: "host" (DataLoader over the RKW files) or
+    #: "device" (the whole set resident in GPU memory, ops/device_data.py;
+    #: `workers` and `in_memory` are ignored)
+    data: str = "host"
+
+    def __post_init__(self):
+        if self.data not in ("host", "device"):
+            raise ValueError(
+                f"data must be 'host' or 'device', got {self.data!r}")
 
 
 MODEL_DTYPES = ("float32", "bfloat16")

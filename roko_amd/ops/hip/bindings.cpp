@@ -140,6 +140,12 @@ void label_windows(const int32_t* ref_start, const int32_t* ref_end,
                    int lo, int hi, const int32_t* pos, int n_windows,
                    uint8_t* labels, uint8_t* keep, int32_t* err,
                    hipStream_t stream);
+void gather_batch(const uint8_t* X, const uint8_t* Y, const int32_t* idx,
+                  uint8_t* out_x, int64_t* out_y, int64_t B,
+                  hipStream_t stream);
+void eval_metrics(const float* logits, const uint8_t* labels, int64_t n,
+                  double inv_n, uint64_t* correct, double* loss_sum,
+                  hipStream_t stream);
 }  // namespace rk
 
 namespace {
@@ -1682,6 +1688,71 @@ uint64_t cu_masked_stream(int64_t reserve_cus) {
     return reinterpret_cast<uint64_t>(s);
 }
 
+// ---------------------------------------------------------------------------
+// Device training data (batch.hip). gather_batch: X (N, 200, 90) u8, Y (N, 90)
+// u8, idx (B) i32 -> out_x[b] = X[idx[b]], out_y[b] = int64(Y[idx[b]]), into
+// caller-owned buffers on the current stream. idx is on the device and is NOT
+// read here: ops/device_data.py checks 0 <= idx < N on the host, once per
+// epoch, before it uploads the permutation.
+void gather_batch(torch::Tensor X, torch::Tensor Y, torch::Tensor idx,
+                  torch::Tensor out_x, torch::Tensor out_y) {
+    check(X, torch::kUInt8, "X");
+    check(Y, torch::kUInt8, "Y");
+    check(idx, torch::kInt32, "idx");
+    check(out_x, torch::kUInt8, "out_x");
+    check(out_y, torch::kInt64, "out_y");
+    TORCH_CHECK(X.dim() == 3 && X.size(1) == 200 && X.size(2) == 90,
+                "X must be (N, 200, 90)");
+    TORCH_CHECK(Y.dim() == 2 && Y.size(0) == X.size(0) && Y.size(1) == 90,
+                "Y must be (N, 90) with X's N");
+    TORCH_CHECK(X.size(0) >= 1, "X holds no windows");
+    TORCH_CHECK(idx.dim() == 1 && idx.size(0) >= 1, "idx must be (B), B >= 1");
+    const int64_t B = idx.size(0);
+    TORCH_CHECK(B < (int64_t(1) << 31), "batch too large");
+    TORCH_CHECK(out_x.dim() == 3 && out_x.size(0) == B &&
+                    out_x.size(1) == 200 && out_x.size(2) == 90,
+                "out_x must be (B, 200, 90)");
+    TORCH_CHECK(out_y.dim() == 2 && out_y.size(0) == B && out_y.size(1) == 90,
+                "out_y must be (B, 90)");
+    TORCH_CHECK(Y.device() == X.device() && idx.device() == X.device() &&
+                    out_x.device() == X.device() &&
+                    out_y.device() == X.device(),
+                "gather_batch tensors must share one device");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(out_x.data_ptr()) % 16 == 0,
+                "X and out_x must be 16-byte aligned");
+    c10::cuda::CUDAGuard guard(X.device());
+    rk::gather_batch(X.data_ptr<uint8_t>(), Y.data_ptr<uint8_t>(),
+                     idx.data_ptr<int32_t>(), out_x.data_ptr<uint8_t>(),
+                     out_y.data_ptr<int64_t>(), B, cur_stream());
+    check_launch("gather_batch kernel");
+}
+
+// eval_metrics: logits (B, 90, 5) f32, labels (B, 90) u8; acc (2) int64 on
+// the Python side: word 0 is the count of correct columns, word 1 holds the
+// bits of a double, the sum of `loss * inv_n` (torch has one dtype per
+// tensor). Adds to acc on the current stream; no host sync.
+void eval_metrics(torch::Tensor logits, torch::Tensor labels, double inv_n,
+                  torch::Tensor acc) {
+    check(logits, torch::kFloat32, "logits");
+    check(labels, torch::kUInt8, "labels");
+    check(acc, torch::kInt64, "acc");
+    TORCH_CHECK(logits.dim() >= 1 && logits.size(-1) == 5,
+                "logits must be (..., 5)");
+    TORCH_CHECK(labels.numel() * 5 == logits.numel(),
+                "labels must hold one class per logits row");
+    TORCH_CHECK(acc.numel() == 2, "acc must hold two 64-bit words");
+    TORCH_CHECK(labels.device() == logits.device() &&
+                    acc.device() == logits.device(),
+                "eval_metrics tensors must share one device");
+    c10::cuda::CUDAGuard guard(logits.device());
+    int64_t* a = acc.data_ptr<int64_t>();
+    rk::eval_metrics(logits.data_ptr<float>(), labels.data_ptr<uint8_t>(),
+                     labels.numel(), inv_n, reinterpret_cast<uint64_t*>(a),
+                     reinterpret_cast<double*>(a + 1), cur_stream());
+    check_launch("eval_metrics kernel");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1780,6 +1851,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("seq_off"), py::arg("cigar"), py::arg("seq4"),
           py::arg("op_rpos"), py::arg("op_qpos"), py::arg("align_index"),
           py::arg("lo"), py::arg("hi"));
+    m.def("gather_batch", &gather_batch, py::arg("X"), py::arg("Y"),
+          py::arg("idx"), py::arg("out_x"), py::arg("out_y"));
+    m.def("eval_metrics", &eval_metrics, py::arg("logits"), py::arg("labels"),
+          py::arg("inv_n"), py::arg("acc"));
     py::class_<ServeSlot>(m, "ServeSlot")
         .def(py::init<py::dict, int, torch::Tensor, int, bool>(),
              py::arg("weights"), py::arg("batch"), py::arg("host_out"),

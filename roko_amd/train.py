@@ -14,11 +14,17 @@ distributed data parallelism:
     (fused front/CE kernels, side-stream weight grads, FusedAdam with one
     flat all-reduce — ops/train.py); ``ROKO_TRAIN_PATH=autograd`` or a batch
     size not divisible by 32 falls back to autograd + torch Adam +
-    GradReducer. CPU always runs the autograd reference path.
+    GradReducer. CPU always runs the autograd reference path;
+  * ``--data device`` (TrainConfig.data) keeps the training and validation
+    sets in GPU memory as stored (18,090 B per window): batches are gathered
+    and validation is scored on the device (ops/device_data.py), and no
+    DataLoader runs. Under torchrun every rank loads the whole set onto its
+    own GPU. The data route does not depend on the step path.
 
 Usage:
   python -m roko_amd.train <train.rkw|dir> <out_dir> [--val v.rkw] [--memory]
       [--t workers] [--b batch] [--epochs N] [--lr LR] [--patience P]
+      [--data host|device]
 """
 
 from __future__ import annotations
@@ -194,28 +200,60 @@ def train(
     rank, local_rank, world = init_distributed()
     if device is None:
         device = torch.device("cuda", local_rank) if torch.cuda.is_available() else torch.device("cpu")
+    if cfg.data == "device" and device.type != "cuda":
+        raise ValueError(
+            "data='device' keeps the training set in GPU memory and needs a "
+            f"GPU device (got {device.type!r}); use data='host'")
     torch.manual_seed(cfg.seed + rank)
 
-    ds_cls = InMemoryTrainDataset if cfg.in_memory else TrainDataset
-    train_ds = ds_cls(train_path)
-    sampler = (
-        DistributedSampler(train_ds, num_replicas=world, rank=rank, seed=cfg.seed)
-        if world > 1
-        else None
-    )
-    train_dl = DataLoader(
-        train_ds,
-        batch_size=cfg.batch_size,
-        shuffle=(sampler is None),
-        sampler=sampler,
-        num_workers=cfg.workers,
-        drop_last=True,
-        pin_memory=torch.cuda.is_available(),
-    )
-    val_dl = None
-    if val_path:
-        val_ds = ds_cls(val_path)
-        val_dl = DataLoader(val_ds, batch_size=cfg.batch_size, num_workers=cfg.workers)
+    train_data = val_data = sampler = train_dl = val_dl = None
+    if cfg.data == "device":
+        from .ops.device_data import (DeviceTrainData, count_rkw_windows,
+                                      epoch_indices, evaluate_device)
+
+        n_val = count_rkw_windows(val_path) if val_path else 0
+        train_data = DeviceTrainData(train_path, device, n_other=n_val)
+        if val_path:
+            val_data = DeviceTrainData(val_path, device)
+        # the step's inputs: one reused pair, so their addresses are stable
+        batch_x = torch.empty((cfg.batch_size, C.WINDOW_ROWS, C.WINDOW_COLS),
+                              dtype=torch.uint8, device=device)
+        batch_y = torch.empty((cfg.batch_size, C.WINDOW_COLS),
+                              dtype=torch.int64, device=device)
+        if rank == 0:
+            sets = [train_data] + ([val_data] if val_data else [])
+            log(f"data: device ({sum(len(d) for d in sets)} windows, "
+                f"{sum(d.nbytes for d in sets) / 1e9:.1f} GB, loaded in "
+                f"{sum(d.load_seconds for d in sets):.1f} s)")
+
+        def epoch_batches(epoch):
+            # the epoch's permutation is range-checked and uploaded once
+            idx = train_data.upload_indices(epoch_indices(
+                len(train_data), cfg.batch_size, cfg.seed, epoch, rank, world))
+            for k in range(0, idx.numel(), cfg.batch_size):
+                train_data.batch(idx[k:k + cfg.batch_size], batch_x, batch_y)
+                yield batch_x, batch_y
+    else:
+        ds_cls = InMemoryTrainDataset if cfg.in_memory else TrainDataset
+        train_ds = ds_cls(train_path)
+        sampler = (
+            DistributedSampler(train_ds, num_replicas=world, rank=rank, seed=cfg.seed)
+            if world > 1
+            else None
+        )
+        train_dl = DataLoader(
+            train_ds,
+            batch_size=cfg.batch_size,
+            shuffle=(sampler is None),
+            sampler=sampler,
+            num_workers=cfg.workers,
+            drop_last=True,
+            pin_memory=torch.cuda.is_available(),
+        )
+        if val_path:
+            val_ds = ds_cls(val_path)
+            val_dl = DataLoader(val_ds, batch_size=cfg.batch_size, num_workers=cfg.workers)
+    has_val = val_dl is not None or val_data is not None
 
     model = RokoModel().to(device)
     use_fused = _select_fused_path(device, cfg)
@@ -258,7 +296,7 @@ def train(
         # device-side loss accumulator: a per-step .item() would sync the
         # stream and stall the fused step's side-stream overlap
         loss_acc = torch.zeros((), device=device)
-        for x, y in train_dl:
+        for x, y in (train_dl if train_data is None else epoch_batches(epoch)):
             x = x.to(device, non_blocking=True)
             y = y.to(device, non_blocking=True)
             if use_fused:
@@ -284,11 +322,14 @@ def train(
         wps = n_batches * cfg.batch_size * world / max(dt, 1e-9)
         run_loss = float(loss_acc.item())
 
-        if val_dl is not None:
+        if val_data is not None:
+            acc, vloss = evaluate_device(model, val_data, cfg.batch_size,
+                                         rank=rank, world=world)
+        elif val_dl is not None:
             acc, vloss = evaluate(model, val_dl, device, rank=rank, world=world)
         else:
             acc, vloss = float("nan"), float("nan")
-        score = acc if val_dl is not None else -run_loss / max(n_batches, 1)
+        score = acc if has_val else -run_loss / max(n_batches, 1)
         history.append(
             {"epoch": epoch, "train_loss": run_loss / max(n_batches, 1),
              "val_acc": acc, "val_loss": vloss, "windows_per_sec": wps}
@@ -302,7 +343,7 @@ def train(
             ckpt.save_state(model, opt, epoch, stopper)
         if max_steps is not None and step >= max_steps:
             break
-        if val_dl is not None and stopper.step(score):
+        if has_val and stopper.step(score):
             if rank == 0:
                 log(f"early stop at epoch {epoch} (no val-acc gain in {cfg.patience})")
             break
@@ -318,8 +359,16 @@ def main(argv=None):
     p.add_argument("train", help="training .rkw file or directory")
     p.add_argument("out", help="checkpoint output directory")
     p.add_argument("--val", default=None, help="validation .rkw")
-    p.add_argument("--memory", action="store_true", help="load dataset to RAM")
-    p.add_argument("--t", type=int, default=0, help="DataLoader workers")
+    p.add_argument("--memory", action="store_true",
+                   help="load dataset to RAM (ignored with --data device)")
+    p.add_argument("--t", type=int, default=0,
+                   help="DataLoader workers (ignored with --data device)")
+    p.add_argument("--data", choices=("host", "device"), default="host",
+                   help="host: DataLoader over the RKW files; device: the "
+                        "training and validation sets resident in GPU memory "
+                        "(18,090 B per window; under torchrun every rank "
+                        "loads the whole set onto its own GPU), batches "
+                        "gathered and validation scored on the device")
     p.add_argument("--b", type=int, default=C.BATCH_SIZE, help="batch size")
     p.add_argument("--epochs", type=int, default=C.EPOCHS)
     p.add_argument("--lr", type=float, default=C.LR)
@@ -331,6 +380,7 @@ def main(argv=None):
     cfg = TrainConfig(
         batch_size=a.b, epochs=a.epochs, lr=a.lr, patience=a.patience,
         workers=a.t, in_memory=a.memory, seed=a.seed, resume=a.resume,
+        data=a.data,
     )
     train(a.train, a.out, val_path=a.val, cfg=cfg)
 
