@@ -182,11 +182,12 @@ def stitch_dense(draft: str, maj: np.ndarray) -> str:
 
 
 def _infer_device_votes(rkw, dl, model, batch_size, depth, meter,
-                        quality=False):
+                        quality=False, edits=None):
     """RKW windows -> DeviceVotes: predictions and vote tables stay on the
     GPU; returns ({contig: polished}, windows, {contig: quality string} or
     None). Positions are fetched per batch from the mmap in runs of one
-    window group."""
+    window group. With a dict `edits` (needs quality) every voted contig's
+    edits (roko_amd/edits.py), compacted on the device, are put into it."""
     from .ops.forward import InferencePipeline
     from .ops.votes import DeviceVotes
 
@@ -231,6 +232,8 @@ def _infer_device_votes(rkw, dl, model, batch_size, depth, meter,
         elif quality:
             from .quality import stitch_dense_qual
 
+            if edits is not None:
+                edits[name] = dv.edits(name, draft)
             out[name], quals[name] = stitch_dense_qual(
                 draft, *dv.consensus_quality(name))
             dv.free(name)
@@ -242,9 +245,13 @@ def _infer_device_votes(rkw, dl, model, batch_size, depth, meter,
 
 def _write_outputs(out: Dict[str, str], quals: Optional[Dict[str, str]],
                    out_path: Optional[str], out_fastq: Optional[str],
-                   log) -> None:
+                   log, out_vcf: Optional[str] = None, refs=None,
+                   edits=None) -> None:
     """FASTA and/or FASTQ of the polished contigs, sorted by name. A contig
-    without an entry in `quals` came through as draft: all Q0."""
+    without an entry in `quals` came through as draft: all Q0. With
+    `out_vcf`, the VCF of `edits` ({contig: edits.EDIT_DTYPE array}) over
+    `refs` ((name, draft) pairs in the draft's order); a contig without an
+    entry has no records, only its ##contig line."""
     if out_path:
         write_fasta(out_path, sorted(out.items()))
         log(f"wrote {len(out)} polished contigs to {out_path}")
@@ -256,6 +263,13 @@ def _write_outputs(out: Dict[str, str], quals: Optional[Dict[str, str]],
                      for name, seq in sorted(out.items())])
         log(f"wrote {len(out)} polished contigs with qualities to "
             f"{out_fastq}")
+    if out_vcf:
+        from .edits import contig_vcf_records, write_vcf
+
+        n = write_vcf(out_vcf, [(name, len(seq)) for name, seq in refs],
+                      contig_vcf_records(refs, edits))
+        log(f"wrote {n} records of "
+            f"{sum(len(e) for e in edits.values())} edits to {out_vcf}")
 
 
 def infer(
@@ -270,6 +284,7 @@ def infer(
     votes: Optional[str] = None,
     depth: int = 48,
     out_fastq: Optional[str] = None,
+    out_vcf: Optional[str] = None,
 ) -> Dict[str, str]:
     """Polish the draft in `data_path` (RKW inference file) and return
     {contig: polished sequence}. Writes FASTA if `out_path` is given.
@@ -281,18 +296,26 @@ def infer(
     votes="device" keeps predictions and vote tables on the GPU
     (ops/votes.py); single process, GPU only. `depth` is the number of
     in-flight batches of the GPU pipeline. `votes` left at None means
-    "host", except that `out_fastq` on a GPU selects "device".
+    "host", except that `out_fastq` or `out_vcf` on a GPU selects "device".
 
     `out_fastq` also writes a FASTQ with a Phred quality per polished base
     (roko_amd/quality.py). Single process only. On a GPU the qualities are
     computed on the device and need votes="device"; on the CPU the host
     route computes them.
+
+    `out_vcf` also writes a VCF of the edits between the draft and the
+    polished sequence (roko_amd/edits.py), under the rules of `out_fastq`:
+    single process; on a GPU the edits are compacted on the device from the
+    vote tables and need votes="device"; on the CPU the numpy reference runs.
     """
     if votes not in (None, "host", "device"):
         raise ValueError(f"votes must be 'host' or 'device', got {votes!r}")
     rank, local_rank, world = init_distributed()
     if out_fastq and world > 1:
         raise ValueError("out_fastq is single-process only "
+                         f"(WORLD_SIZE={world}); run one process")
+    if out_vcf and world > 1:
+        raise ValueError("out_vcf is single-process only "
                          f"(WORLD_SIZE={world}); run one process")
     if votes == "device" and world > 1:
         raise ValueError("votes='device' is single-process only "
@@ -304,15 +327,18 @@ def infer(
             else torch.device("cpu")
         )
     device = torch.device(device)
-    if out_fastq and device.type == "cuda":
+    if (out_fastq or out_vcf) and device.type == "cuda":
         if votes == "host":
             raise ValueError(
-                "out_fastq on a GPU computes the qualities on the device "
+                f"{'out_fastq' if out_fastq else 'out_vcf'} on a GPU "
+                "computes the qualities on the device "
                 "and needs votes='device' (or leave votes unset)")
         votes = "device"
     if votes is None:
         votes = "host"
-    quality = bool(out_fastq)
+    # the edits carry qualities, so a VCF turns the quality tables on
+    quality = bool(out_fastq or out_vcf)
+    edits: Optional[Dict[str, np.ndarray]] = {} if out_vcf else None
 
     if model is None:
         model = RokoModel()
@@ -358,7 +384,7 @@ def infer(
     with torch.no_grad():
         if votes == "device":
             out, n_windows, quals = _infer_device_votes(
-                rkw, dl, model, batch_size, depth, meter, quality)
+                rkw, dl, model, batch_size, depth, meter, quality, edits)
         elif pipe is not None:
             # pipelined: keep `depth` batches in flight; votes are harvested
             # one pipeline-depth behind submission
@@ -392,8 +418,11 @@ def infer(
         f"({bases / max(dt, 1e-9):.0f} bases/s)"
     )
 
+    refs = [(name, rkw.contig_seq(name)) for name in rkw.contig_names()] \
+        if out_vcf else None
     if out is not None:
-        _write_outputs(out, quals, out_path, out_fastq, log)
+        _write_outputs(out, quals, out_path, out_fastq, log, out_vcf, refs,
+                       edits)
         return out
 
     if quality:
@@ -427,9 +456,14 @@ def infer(
                     raise RuntimeError(
                         f"{name}: the quality stitch disagrees with the "
                         "sequence stitch")
+                if edits is not None:
+                    from .edits import table_edits
+
+                    edits[name] = table_edits(draft, tables[name],
+                                              sums[name])
         else:
             out[name] = draft
-    _write_outputs(out, quals, out_path, out_fastq, log)
+    _write_outputs(out, quals, out_path, out_fastq, log, out_vcf, refs, edits)
     return out
 
 
@@ -444,9 +478,13 @@ def main(argv=None):
                    help="also write FASTQ with a Phred quality per polished "
                         "base (single process; on a GPU the votes run on "
                         "the device)")
+    p.add_argument("--vcf", default=None, metavar="PATH",
+                   help="also write VCF: the edits between the draft and "
+                        "the polished sequence (single process; on a GPU "
+                        "the votes run on the device)")
     a = p.parse_args(argv)
     infer(a.data, a.model, a.out, batch_size=a.b, workers=a.t,
-          out_fastq=a.fastq)
+          out_fastq=a.fastq, out_vcf=a.vcf)
 
 
 if __name__ == "__main__":

@@ -110,6 +110,13 @@ void vote_scatter_q(const uint8_t* preds, const uint8_t* units,
 void vote_consensus_q(const uint32_t* table, const uint64_t* qsum,
                       int64_t n_slots, uint8_t* maj, uint8_t* qual,
                       hipStream_t stream);
+int64_t edit_num_blocks(int64_t n_pos);
+void edit_count(const uint32_t* table, const uint8_t* draft, int64_t n_pos,
+                int64_t* state, int64_t* counts, hipStream_t stream);
+void edit_write(const uint32_t* table, const uint64_t* qsum,
+                const uint8_t* draft, int64_t n_pos, const int64_t* state,
+                const int64_t* offsets, void* records, int64_t total,
+                hipStream_t stream);
 bool windows_geometry_ok(int rows, int cols, int stride, int max_ins);
 void windows_index(const int32_t* ref_start, const int32_t* ref_end,
                    const uint8_t* reverse, const uint32_t* cigar_off,
@@ -923,6 +930,70 @@ void vote_consensus_q(torch::Tensor table, torch::Tensor qsum,
     rk::vote_consensus_q(tab, qs, n_slots, maj.data_ptr<uint8_t>(),
                          qual.data_ptr<uint8_t>(), cur_stream());
     check_launch("vote kernel");
+}
+
+// ---------------------------------------------------------------------------
+// Polishing edits (edits.hip). `state` is int64[3] {s0, last voted slot,
+// total}, set to {INT64_MAX, -1, 0} by the caller; `counts` holds one int64
+// per 256-position workgroup and comes back as the workgroups' record
+// offsets. The table holds exactly 4 slots per draft byte.
+const uint8_t* edit_draft_ptr(const torch::Tensor& draft, int64_t n_slots) {
+    check(draft, torch::kUInt8, "draft");
+    TORCH_CHECK(draft.numel() * 4 == n_slots,
+                "the table must hold 4 slots per draft byte");
+    return draft.data_ptr<uint8_t>();
+}
+
+int64_t* edit_state_ptr(const torch::Tensor& state) {
+    check(state, torch::kInt64, "state");
+    TORCH_CHECK(state.numel() == 3, "state must hold three int64");
+    return state.data_ptr<int64_t>();
+}
+
+int64_t* edit_counts_ptr(const torch::Tensor& counts, int64_t n_pos) {
+    check(counts, torch::kInt64, "counts");
+    TORCH_CHECK(counts.numel() == rk::edit_num_blocks(n_pos),
+                "counts must hold one int64 per workgroup");
+    return counts.data_ptr<int64_t>();
+}
+
+int64_t edit_num_blocks(int64_t n_pos) {
+    TORCH_CHECK(n_pos >= 0, "negative length");
+    return rk::edit_num_blocks(n_pos);
+}
+
+// bounds + per-workgroup counts + their exclusive scan, three kernels
+void edit_count(torch::Tensor table, torch::Tensor draft, int64_t n_slots,
+                torch::Tensor state, torch::Tensor counts) {
+    uint32_t* tab = vote_table_ptr(table, n_slots);
+    const uint8_t* dr = edit_draft_ptr(draft, n_slots);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(tab) % 16 == 0,
+                "vote tables must be 16-byte aligned");
+    const int64_t n_pos = draft.numel();
+    rk::edit_count(tab, dr, n_pos, edit_state_ptr(state),
+                   edit_counts_ptr(counts, n_pos), cur_stream());
+    check_launch("edit kernel");
+}
+
+// the records, `total` of them (state[2] as read back by the caller), 16
+// bytes each, into `records` (int64, 2 words per record)
+void edit_write(torch::Tensor table, torch::Tensor qsum, torch::Tensor draft,
+                int64_t n_slots, torch::Tensor state, torch::Tensor offsets,
+                torch::Tensor records, int64_t total) {
+    uint32_t* tab = vote_table_ptr(table, n_slots);
+    uint64_t* qs = vote_qsum_ptr(qsum, n_slots);
+    const uint8_t* dr = edit_draft_ptr(draft, n_slots);
+    check(records, torch::kInt64, "records");
+    TORCH_CHECK(total >= 0 && records.numel() == 2 * total,
+                "records must hold two int64 per edit");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(tab) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(records.data_ptr()) % 16 == 0,
+                "vote tables and records must be 16-byte aligned");
+    const int64_t n_pos = draft.numel();
+    rk::edit_write(tab, qs, dr, n_pos, edit_state_ptr(state),
+                   edit_counts_ptr(offsets, n_pos), records.data_ptr(), total,
+                   cur_stream());
+    check_launch("edit kernel");
 }
 
 // ---------------------------------------------------------------------------
@@ -1837,6 +1908,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("vote_consensus_q", &vote_consensus_q, py::arg("table"),
           py::arg("qsum"), py::arg("n_slots"), py::arg("maj"),
           py::arg("qual"));
+    m.def("edit_num_blocks", &edit_num_blocks, py::arg("n_pos"));
+    m.def("edit_count", &edit_count, py::arg("table"), py::arg("draft"),
+          py::arg("n_slots"), py::arg("state"), py::arg("counts"));
+    m.def("edit_write", &edit_write, py::arg("table"), py::arg("qsum"),
+          py::arg("draft"), py::arg("n_slots"), py::arg("state"),
+          py::arg("offsets"), py::arg("records"), py::arg("total"));
     m.def("build_windows", &build_windows, py::arg("ref_start"),
           py::arg("ref_end"), py::arg("reverse"), py::arg("cigar_off"),
           py::arg("seq_off"), py::arg("cigar"), py::arg("seq4"),

@@ -13,13 +13,9 @@
 #include <cstdint>
 
 #include "common.h"
+#include "votes.h"  // table formats, vote_majority, vote_quality
 
 namespace rk {
-
-constexpr int VOTE_CLASSES = 5;
-constexpr int VOTE_INS_SLOTS = 4;  // MAX_INS + 1
-constexpr uint32_t VOTE_ERR_RANGE = 1u;     // pos / ins / class out of range
-constexpr uint32_t VOTE_ERR_OVERFLOW = 2u;  // a 4-bit counter was already 15
 
 // One thread per (window, column). Rows with pos < 0 are padding and do not
 // vote. Integer adds commute, so the table is exact and reproducible whatever
@@ -50,19 +46,6 @@ __global__ __launch_bounds__(256) void vote_scatter_kernel(
                               __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// majority class of one packed slot; ties -> smallest class id (the strict
-// '>' keeps the first maximum, as numpy's argmax does); no votes -> 0xFF
-RK_DEV uint32_t vote_majority(uint32_t v) {
-    if (v == 0u) return 0xFFu;
-    uint32_t best = 0, bc = v & 15u;
-#pragma unroll
-    for (uint32_t c = 1; c < VOTE_CLASSES; ++c) {
-        const uint32_t n = (v >> (4 * c)) & 15u;
-        if (n > bc) { bc = n; best = c; }
-    }
-    return best;
-}
-
 // One thread per 4 slots: one 16-byte load, one packed 4-byte store (a wave
 // reads 1 KiB and writes 256 B, both contiguous). The last, partial group
 // goes slot by slot.
@@ -90,11 +73,7 @@ __global__ __launch_bounds__(256) void vote_consensus_kernel(
 // both the extractor's bound (6 votes) and the count table's (15 per class)
 // fit; a field that would pass 4095 is seen in the atomic's return value and
 // sets VOTE_ERR_OVERFLOW.
-constexpr int QSUM_BITS = 12;
-constexpr uint64_t QSUM_MASK = (1ull << QSUM_BITS) - 1;
-constexpr uint32_t QUAL_UNITS_PER_Q = 4;
-constexpr uint32_t QUAL_MAX = 60;
-constexpr uint32_t NO_QUAL = 0xFFu;
+// (constants and the per-slot readers: votes.h)
 
 // vote_scatter_kernel plus one 64-bit add of the five packed units: same
 // guard, same padding rule, same relaxed agent-scope atomics.
@@ -137,18 +116,6 @@ __global__ __launch_bounds__(256) void vote_scatter_q_kernel(
     if (over)
         __hip_atomic_fetch_or(err_flag, VOTE_ERR_OVERFLOW, __ATOMIC_RELAXED,
                               __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// quality of one slot: the called class's mean Phred over ALL votes of the
-// slot, Q = min(60, S_c / (4 n)); no votes -> NO_QUAL
-RK_DEV uint32_t vote_quality(uint32_t v, unsigned long long q, uint32_t maj) {
-    if (v == 0u) return NO_QUAL;
-    uint32_t n = 0;
-#pragma unroll
-    for (uint32_t c = 0; c < VOTE_CLASSES; ++c) n += (v >> (4 * c)) & 15u;
-    const uint32_t s = (uint32_t)((q >> (QSUM_BITS * maj)) & QSUM_MASK);
-    const uint32_t ql = s / (QUAL_UNITS_PER_Q * n);
-    return ql < QUAL_MAX ? ql : QUAL_MAX;
 }
 
 // One thread per 4 slots: one 16-byte load of counts, two of qsum, packed

@@ -18,6 +18,11 @@ base), class k in the 12-bit field at bits [12k, 12k+12) holding the sum of
 that class's quarter-Phred units over the slot's votes. 16 votes x 255 = 4080
 < 4096, so whatever the count table holds fits; a field that would pass 4095
 sets the same overflow flag.
+
+Edits (`edits()`, kernels: ops/hip/edits.hip, contract: roko_amd/edits.py):
+from both tables and the draft, the slots at which the polished sequence
+differs from the draft, compacted on the device in slot order; only they are
+copied back.
 """
 
 from __future__ import annotations
@@ -35,6 +40,12 @@ _NIBBLE = 4
 _QFIELD = 12  # bits per class in a qsum word
 _ERR_RANGE = 1
 _ERR_OVERFLOW = 2
+_I64_MAX = (1 << 63) - 1
+# device edit record (ops/hip/edits.hip): the fields of edits.EDIT_DTYPE in 16
+# bytes
+_EDIT_RECORD = np.dtype({"names": ["pos", "ins", "ref", "alt", "qual"],
+                         "formats": ["<i8", "u1", "u1", "u1", "u1"],
+                         "offsets": [0, 8, 9, 10, 11], "itemsize": 16})
 
 
 class VoteOverflowError(RuntimeError):
@@ -252,3 +263,42 @@ class DeviceVotes:
         self.ext.vote_consensus_q(self.table(contig), self.qsum(contig), n,
                                   maj, qual)
         return maj.cpu().numpy(), qual.cpu().numpy()
+
+    def edits(self, contig: str, draft: str) -> np.ndarray:
+        """What polishing changes in `draft`: edits.dense_edits(draft,
+        *consensus_quality(contig)) computed on the device (ops/hip/
+        edits.hip), in slot order, as an array of edits.EDIT_DTYPE. The draft
+        goes up once (a byte per base); what comes back is three words and
+        then 16 bytes per edit, never the dense arrays."""
+        from ..edits import EDIT_DTYPE
+
+        self._need_quality()
+        self._check()
+        n_pos = self.lens[contig]
+        if len(draft) != n_pos:
+            raise ValueError(f"{contig}: draft of {len(draft)} bases for "
+                             f"tables of {n_pos}")
+        if n_pos == 0 or not self.has_votes(contig):
+            return np.empty(0, dtype=EDIT_DTYPE)
+        n = self.n_slots(contig)
+        table, qsum = self.table(contig), self.qsum(contig)
+        d = torch.from_numpy(
+            np.frombuffer(bytearray(draft, "ascii"), dtype=np.uint8)
+        ).to(self.device)
+        # {first voted ins == 0 slot, last voted slot, number of edits}
+        state = torch.tensor([_I64_MAX, -1, 0], dtype=torch.int64) \
+            .to(self.device)
+        offsets = torch.empty(self.ext.edit_num_blocks(n_pos),
+                              dtype=torch.int64, device=self.device)
+        self.ext.edit_count(table, d, n, state, offsets)
+        total = int(state.cpu()[2])
+        if total == 0:
+            return np.empty(0, dtype=EDIT_DTYPE)
+        records = torch.empty(2 * total, dtype=torch.int64,
+                              device=self.device)
+        self.ext.edit_write(table, qsum, d, n, state, offsets, records, total)
+        rec = records.cpu().numpy().view(_EDIT_RECORD)
+        out = np.empty(total, dtype=EDIT_DTYPE)
+        for name in EDIT_DTYPE.names:
+            out[name] = rec[name]
+        return out

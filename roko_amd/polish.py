@@ -2,7 +2,7 @@
 
   python -m roko_amd.polish <draft.fasta> <reads.bam> <model.pth> <out.fasta>
       [--t workers] [--b batch] [--seed N] [--extract host|device]
-      [--sampler mt19937|counter] [--fastq out.fastq]
+      [--sampler mt19937|counter] [--fastq out.fastq] [--vcf out.vcf]
 
 Does what `features` followed by `inference` does, and writes the same FASTA
 byte for byte, without the RKW file between them: region windows stream from
@@ -24,6 +24,14 @@ quality per polished base (roko_amd/quality.py), computed on the device on
 every GPU route and by the numpy reference on the CPU route. Draft bases that
 are copied through unpolished get Q0; a deleted base leaves no trace in the
 quality string.
+
+With --vcf PATH a VCF 4.2 of what polishing changed is written as well
+(roko_amd/edits.py): every substituted, deleted or inserted draft base with
+its quality, adjacent edits merged into one record. A draft base that the
+stitch drops because no window covered it is a deletion flagged NOCOV. On
+the GPU routes the edits are compacted on the device from the vote tables
+(ops/hip/edits.hip) and only they come back; the CPU route runs the numpy
+reference. The FASTA and FASTQ do not depend on it.
 
 Single process only; for multi-GPU runs use `features` + `inference` under
 torchrun.
@@ -58,13 +66,15 @@ class _DeviceSink:
     stitched from its consensus bytes as soon as its last region is in."""
 
     def __init__(self, model, batch: int, depth: int, lens: Dict[str, int],
-                 quality: bool = False):
+                 quality: bool = False, want_edits: bool = False):
         from .ops.forward import InferencePipeline
         from .ops.votes import DeviceVotes
 
         self.batch = batch
         self.quality = quality
         self.quals: Dict[str, str] = {}  # contig -> quality string
+        self.want_edits = want_edits  # needs quality
+        self.edits: Dict[str, np.ndarray] = {}  # contig -> edits.EDIT_DTYPE
         # votes mode runs one batch per slot (coalesce=1)
         self.dv = DeviceVotes(lens, InferencePipeline(model, batch,
                                                       depth=depth,
@@ -100,6 +110,8 @@ class _DeviceSink:
             self._submit(contig)  # a slot batch votes into one contig's table
         if not self.dv.has_votes(contig):
             return draft
+        if self.want_edits:
+            self.edits[contig] = self.dv.edits(contig, draft)  # drains first
         if self.quality:
             from .quality import stitch_dense_qual
 
@@ -121,8 +133,8 @@ class _DeviceBuildSink(_DeviceSink):
     windows. A region's last slice may be short."""
 
     def __init__(self, model, batch, depth, lens, cfg, device,
-                 quality=False):
-        super().__init__(model, batch, depth, lens, quality)
+                 quality=False, want_edits=False):
+        super().__init__(model, batch, depth, lens, quality, want_edits)
         self.cfg, self.device = cfg, device
 
     def add_reads(self, contig: str, pack: dict) -> int:
@@ -144,13 +156,15 @@ class _HostSink:
     batches. Contigs are stitched at the end."""
 
     def __init__(self, model, batch: int, device, drafts: Dict[str, str],
-                 quality: bool = False):
+                 quality: bool = False, want_edits: bool = False):
         from .inference import StreamingVotes
 
         self.model, self.batch, self.device = model, batch, device
         self.drafts = drafts
         self.quality = quality
         self.quals: Dict[str, str] = {}  # contig -> quality string
+        self.want_edits = want_edits  # needs quality
+        self.edits: Dict[str, np.ndarray] = {}  # contig -> edits.EDIT_DTYPE
         if quality:
             from .quality import StreamingQualityVotes
 
@@ -220,6 +234,11 @@ class _HostSink:
             if seq != out[name]:
                 raise RuntimeError(f"{name}: the quality stitch disagrees "
                                    "with the sequence stitch")
+            if self.want_edits:
+                from .edits import table_edits
+
+                self.edits[name] = table_edits(self.drafts[name],
+                                               tables[name], sums[name])
         return out
 
 
@@ -237,10 +256,12 @@ def polish(
     depth: int = 16,
     extract: str = "host",
     out_fastq: Optional[str] = None,
+    out_vcf: Optional[str] = None,
 ) -> Dict[str, str]:
     """Polish `draft_fasta` with the reads in `reads_bam`; returns {contig:
-    polished sequence} and writes FASTA if `out_fasta` is given, and FASTQ
-    with a Phred quality per polished base if `out_fastq` is. Regions,
+    polished sequence} and writes FASTA if `out_fasta` is given, FASTQ
+    with a Phred quality per polished base if `out_fastq` is, and a VCF of
+    the edits between draft and polished sequence if `out_vcf` is. Regions,
     FeatureConfig and seeding are those of `features.run`; `depth` is the
     number of in-flight batches on the GPU. `extract="device"` builds the
     windows on the GPU from packed reads (counter sampler, whatever
@@ -273,7 +294,7 @@ def polish(
     try:
         return _polish(refs, jobs, pool, model_path, out_fasta, workers,
                        batch_size, device, model, log, depth, extract, cfg,
-                       out_fastq)
+                       out_fastq, out_vcf)
     finally:
         if pool is not None:
             pool.terminate()
@@ -291,7 +312,7 @@ def _device_type(device) -> str:
 
 def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
             device, model, log, depth, extract, cfg,
-            out_fastq=None) -> Dict[str, str]:
+            out_fastq=None, out_vcf=None) -> Dict[str, str]:
     import torch
 
     from .model import RokoModel
@@ -305,16 +326,19 @@ def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
     model = model.to(device).eval()
 
     drafts = dict(refs)
-    quality = bool(out_fastq)
+    # the edits carry qualities, so a VCF turns the quality tables on
+    quality = bool(out_fastq or out_vcf)
+    want_edits = bool(out_vcf)
     if extract == "device":
         sink = _DeviceBuildSink(model, batch_size, depth,
                                 {n: len(s) for n, s in refs}, cfg, device,
-                                quality)
+                                quality, want_edits)
     elif device.type == "cuda":
         sink = _DeviceSink(model, batch_size, depth,
-                           {n: len(s) for n, s in refs}, quality)
+                           {n: len(s) for n, s in refs}, quality, want_edits)
     else:
-        sink = _HostSink(model, batch_size, device, drafts, quality)
+        sink = _HostSink(model, batch_size, device, drafts, quality,
+                         want_edits)
     worker = generate_reads if extract == "device" else generate_infer
     log(f"polish: {len(jobs)} region jobs, {workers} workers, "
         f"batch {batch_size}, windows on {extract}, votes on {device.type}")
@@ -377,6 +401,14 @@ def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
                      for name, seq in sorted(out.items())])
         log(f"wrote {len(out)} polished contigs with qualities to "
             f"{out_fastq}")
+    if out_vcf:
+        from .edits import contig_vcf_records, write_vcf
+
+        # a contig without windows has no edits, only its ##contig line
+        n = write_vcf(out_vcf, [(name, len(seq)) for name, seq in refs],
+                      contig_vcf_records(refs, sink.edits))
+        log(f"wrote {n} records of "
+            f"{sum(len(e) for e in sink.edits.values())} edits to {out_vcf}")
     return out
 
 
@@ -399,10 +431,13 @@ def main(argv=None):
     p.add_argument("--fastq", default=None, metavar="PATH",
                    help="also write FASTQ: the same sequences with a Phred "
                         "quality per polished base")
+    p.add_argument("--vcf", default=None, metavar="PATH",
+                   help="also write VCF: the edits between the draft and "
+                        "the polished sequence, with their qualities")
     a = p.parse_args(argv)
     polish(a.draft, a.bam, a.model, a.out, workers=a.t, batch_size=a.b,
            cfg=FeatureConfig(seed=a.seed, sampler=a.sampler),
-           extract=a.extract, out_fastq=a.fastq)
+           extract=a.extract, out_fastq=a.fastq, out_vcf=a.vcf)
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""End-to-end polishing rate: draft + BAM -> FASTA, five ways.
+"""End-to-end polishing rate: draft + BAM -> FASTA, six ways.
 
   python scripts/polish_bench.py [--ref-len N] [--cov C] [--t WORKERS]
       [--b BATCH] [--limit SECONDS] [--dir DIR] [--routes a,b,...]
@@ -13,6 +13,8 @@ _make_case, size given by --ref-len), then times
   polish_host_counter   polish with the counter row sampler
   polish_device         polish(extract="device"): workers pack reads, the
                         windows are built on the GPU (counter sampler)
+  polish_device_vcf     polish_device with out_vcf: quality tables on, the
+                        edits compacted on the GPU, the VCF written
 
 --routes picks a subset; --repeat N runs the chosen routes N times in turn
 (a, b, a, b, ...), so that drift of the machine hits all of them alike.
@@ -45,7 +47,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEPS = ("two_step", "infer_device", "polish")
-COUNTER_STEPS = ("polish_host_counter", "polish_device")
+COUNTER_STEPS = ("polish_host_counter", "polish_device",
+                 "polish_device_vcf")
 ALL_STEPS = STEPS + COUNTER_STEPS
 
 
@@ -95,6 +98,10 @@ def run_step(step, d, workers, batch, region, fastq=False):
         out_fastq = os.path.join(d, f"{step}.fastq")
         rec.update(fastq=True,
                    qsum_bytes=8 * (C.MAX_INS + 1) * draft_bases)
+    out_vcf = None
+    if step == "polish_device_vcf":
+        out_vcf = os.path.join(d, f"{step}.vcf")
+        rec.update(vcf=True)
     t0 = time.time()
     if step.startswith("polish"):
         from roko_amd.polish import LAST_RUN
@@ -103,8 +110,9 @@ def run_step(step, d, workers, batch, region, fastq=False):
             cfg.sampler = "counter"
         polish(draft, bam, ckpt, out, workers=workers, batch_size=batch,
                cfg=cfg, log=quiet,
-               extract="device" if step == "polish_device" else "host",
-               out_fastq=out_fastq)
+               extract="device" if step.startswith("polish_device")
+               else "host",
+               out_fastq=out_fastq, out_vcf=out_vcf)
         n = LAST_RUN["windows"]
     else:
         rkw = os.path.join(d, f"{step}.rkw")
@@ -116,6 +124,11 @@ def run_step(step, d, workers, batch, region, fastq=False):
               out_fastq=out_fastq)
         rec["infer_s"] = round(time.time() - t1, 3)
     wall = time.time() - t0
+    if out_vcf:
+        with open(out_vcf) as fh:
+            ne = [int(line.rsplit("NE=", 1)[1].split(";")[0]) for line in fh
+                  if not line.startswith("#")]
+        rec.update(vcf_records=len(ne), vcf_edits=sum(ne))
     rec.update(windows=n, wall_s=round(wall, 3),
                windows_per_s=round(n / wall, 1),
                bases_per_s=round(draft_bases / wall, 1),
