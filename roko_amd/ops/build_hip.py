@@ -21,8 +21,11 @@ def build():
 
     build_dir = os.path.join(HERE, "_build")
     os.makedirs(build_dir, exist_ok=True)
-    names = ["bindings.cpp", "adam.hip", "batch.hip", "ce.hip", "edits.hip", "embed_mlp.hip", "embgrad.hip", "front_train.hip", "gemm.hip",
-             "gru.hip", "head.hip", "probe.hip", "votes.hip", "windows.hip"]
+    names = ["bindings.cpp", "bind_model.cpp", "bind_train.cpp",
+             "bind_data.cpp", "serve_slot.cpp",
+             "adam.hip", "batch.hip", "ce.hip", "edits.hip", "embed_mlp.hip",
+             "embgrad.hip", "front_train.hip", "gemm.hip", "gru.hip",
+             "head.hip", "probe.hip", "votes.hip", "windows.hip"]
     sources = [os.path.join(HERE, "hip", n) for n in names]
     load(
         name="_hip_ops",

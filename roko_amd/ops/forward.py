@@ -29,13 +29,13 @@ def _front_eval(ext, ids, w):
     if _FRONT == "shared":
         return ext.front_fwd(ids, w["w1"], w["b1"], w["w2"], w["b2"],
                              w["emb"], 0, 1.0)
-    if _FRONT == "v1" or not hasattr(ext, "embed_mlp_fwd2"):
+    if _FRONT == "v1":
         return ext.embed_mlp_fwd(ids, w["w1"], w["b1"], w["w2"], w["b2"],
                                  w["emb"])
     if _FRONT == "v4":
         return ext.embed_mlp_fwd4(ids, w["w1g"], w["b1"], w["w2"], w["b2"],
                                   w["emb"])
-    if _FRONT == "v3" and hasattr(ext, "embed_mlp_fwd3"):
+    if _FRONT == "v3":
         return ext.embed_mlp_fwd3(ids, w["w1g"], w["b1"], w["w2"], w["b2"],
                                   w["emb"])
     return ext.embed_mlp_fwd2(ids, w["w1g"], w["b1"], w["w2"], w["b2"],
@@ -106,18 +106,22 @@ def _bf16_weights(model) -> dict:
     return c
 
 
-def roko_forward(model, x: torch.Tensor) -> torch.Tensor:
-    """ids (B, 200, 90) int/uint8 on GPU -> logits (B, 90, 5) fp32."""
-    ext = _ext()
-    w = _bf16_weights(model)
-    B0 = x.shape[0]
+def _pad32(x: torch.Tensor) -> torch.Tensor:
+    """ids as contiguous uint8, zero rows appended up to a multiple of 32."""
     ids = x.to(torch.uint8).contiguous()
-    pad = (-B0) % 32
+    pad = (-ids.shape[0]) % 32
     if pad:
         ids = torch.cat([ids, ids.new_zeros(pad, *ids.shape[1:])])
+    return ids
+
+
+def _forward(model, ids: torch.Tensor, logits: bool) -> torch.Tensor:
+    """front -> 3 x (addmm + GRU) -> head on padded ids (B % 32 == 0):
+    logits (B, 90, 5) fp32, or the fused argmax (B, 90) uint8."""
+    ext = _ext()
+    w = _bf16_weights(model)
     B = ids.shape[0]
     T = C.WINDOW_COLS
-
     seq = _front_eval(ext, ids, w)
     for l in range(C.NUM_LAYERS):
         xg = torch.addmm(
@@ -125,8 +129,18 @@ def roko_forward(model, x: torch.Tensor) -> torch.Tensor:
         ).view(T, B, 2, 384)
         (hseq,) = ext.gru_layer_fwd(xg.contiguous(), w[f"u{l}"], w[f"bhh{l}"], False)
         seq = hseq.view(T, B, 2 * C.HIDDEN_SIZE)
-    (logits,) = ext.head_fwd(seq, w["w4"], w["b4"], True, False)
-    return logits[:B0]
+    (out,) = ext.head_fwd(seq, w["w4"], w["b4"], logits, not logits)
+    return out
+
+
+def roko_forward(model, x: torch.Tensor) -> torch.Tensor:
+    """ids (B, 200, 90) int/uint8 on GPU -> logits (B, 90, 5) fp32."""
+    return _forward(model, _pad32(x), True)[: x.shape[0]]
+
+
+def roko_argmax(model, x: torch.Tensor) -> torch.Tensor:
+    """ids -> per-position class predictions (B, 90) uint8, argmax fused."""
+    return _forward(model, _pad32(x), False)[: x.shape[0]]
 
 
 #: shipped coalescing request (ROKO_COALESCE overrides): consecutive
@@ -157,8 +171,8 @@ class InferencePipeline:
     >= 256 the slot auto-captures its kernel sequence into a RAW hipGraph
     (BASELINE.json config 4's "hipGraph-captured GRU steps") — a measured
     win at large batch and a measured loss at b=128, both A/B'd
-    (profiles/PERF_HISTORY.md; ROKO_GSLOT overrides). The older
-    torch-level graph backend is kept as ROKO_SERVE=graph for A/B.
+    (profiles/PERF_HISTORY.md; ROKO_GSLOT overrides). What a slot chose to
+    launch is its `cpp.plan`.
 
     Every submitted batch runs the full model; nothing is cached or skipped
     — pipelining only overlaps independent batches, as a serving deployment
@@ -183,8 +197,7 @@ class InferencePipeline:
     <= 32 keeps that true for the benchmark. Votes mode needs G=1.
     """
 
-    def __init__(self, model, batch: int, depth: int = 4,
-                 use_graphs: bool = True, coalesce=None,
+    def __init__(self, model, batch: int, depth: int = 4, coalesce=None,
                  quality: bool = False):
         from . import require
 
@@ -193,7 +206,6 @@ class InferencePipeline:
         self.depth = depth
         self.model = model
         self.w = _bf16_weights(model)
-        self.use_graphs = use_graphs
         # quality=True: the slots' head kernel also writes five quality
         # units per column (roko_amd/quality.py) for the votes mode; fixed
         # at construction, and off it leaves the slots exactly as they were
@@ -201,15 +213,7 @@ class InferencePipeline:
         dev = next(model.parameters()).device
         if coalesce is None:
             coalesce = int(os.environ.get("ROKO_COALESCE", _COALESCE_DEFAULT))
-        # only the C++ slot can be filled in parts
-        cpp_ok = use_graphs and os.environ.get("ROKO_SERVE") != "graph" \
-            and hasattr(_ext(), "ServeSlot")
-        if self.quality and not cpp_ok:
-            raise RuntimeError(
-                "quality output needs the C++ serving slot (ext.ServeSlot); "
-                "it is not available with ROKO_SERVE=graph or "
-                "use_graphs=False")
-        self.coalesce = coalesce_width(coalesce, depth) if cpp_ok else 1
+        self.coalesce = coalesce_width(coalesce, depth)
         self.slots = []
         for _ in range(depth // self.coalesce):
             self.slots.append(_Slot(self, batch, dev, self.coalesce))
@@ -223,26 +227,7 @@ class InferencePipeline:
 
     def unlaunched(self) -> int:
         """Submitted batches whose model launch is still deferred."""
-        return sum(s.cpp.unlaunched() for s in self.slots
-                   if s.cpp is not None)
-
-    def _forward_amax(self, ids_u8: torch.Tensor) -> torch.Tensor:
-        """Static-shape argmax forward (body of roko_argmax, no padding)."""
-        ext = _ext()
-        w = self.w
-        B = ids_u8.shape[0]
-        T = C.WINDOW_COLS
-        seq = _front_eval(ext, ids_u8, w)
-        for l in range(C.NUM_LAYERS):
-            xg = torch.addmm(
-                w[f"b_ih{l}"], seq.reshape(T * B, -1), w[f"w_ih_t{l}"]
-            ).view(T, B, 2, 384)
-            (hseq,) = ext.gru_layer_fwd(
-                xg.contiguous(), w[f"u{l}"], w[f"bhh{l}"], False
-            )
-            seq = hseq.view(T, B, 2 * C.HIDDEN_SIZE)
-        (amax,) = ext.head_fwd(seq, w["w4"], w["b4"], False, True)
-        return amax
+        return sum(s.cpp.unlaunched() for s in self.slots)
 
     def submit(self, x: torch.Tensor, copy_out: bool = True):
         """Enqueue one batch (device or host tensor, (<=batch, R, W) int).
@@ -333,23 +318,18 @@ class _Ticket:
 
 
 class _Slot:
-    """One pipeline slot. Two serving backends:
-
-    * C++ fast path (default): an `ext.ServeSlot` owns the slot stream and
-      enqueues the whole forward (input copy, front kernel, 3x xg GEMM + GRU,
-      fused head+argmax, pinned D2H) in ONE pybind call. The server is
-      host-bound — a torch hipGraph replay costs ~51 us + ~15 us/node of
-      host time on ROCm and threads don't scale (runtime-global enqueue
-      lock) — so per-batch Python work IS the throughput limit
-      (profiles/PERF_HISTORY.md).
-    * hipGraph path (ROKO_SERVE=graph): each slot's forward captured once
-      and replayed per batch; kept for A/B and as the reference backend.
-    """
+    """One pipeline slot: an `ext.ServeSlot` owns the slot stream and
+    enqueues the whole forward (input copy, front kernel, 3x xg GEMM + GRU,
+    fused head+argmax, pinned D2H) in ONE pybind call. The server is
+    host-bound (a torch hipGraph replay costs ~51 us + ~15 us/node of host
+    time on ROCm and threads don't scale: runtime-global enqueue lock), so
+    per-batch Python work IS the throughput limit
+    (profiles/PERF_HISTORY.md)."""
 
     def __init__(self, pipe: "InferencePipeline", batch: int, dev,
                  parts: int = 1):
-        # `parts` consecutive submissions of `batch` rows share this slot
-        # (C++ backend only); the slot is `parts * batch` rows wide
+        # `parts` consecutive submissions of `batch` rows share this slot;
+        # the slot is `parts * batch` rows wide
         self.pipe = pipe
         self.bp = batch
         self.parts = parts
@@ -359,48 +339,17 @@ class _Slot:
         self.host_out = torch.empty(
             (batch, C.WINDOW_COLS), dtype=torch.uint8, pin_memory=True
         )
-        self.cpp = None
-        self.graph = None
-        ext = _ext()
-        if pipe.use_graphs and os.environ.get("ROKO_SERVE") != "graph" \
-                and hasattr(ext, "ServeSlot"):
-            if pipe.quality:
-                self.cpp = ext.ServeSlot(self.pipe.w, batch, self.host_out,
-                                         parts, True)
-            else:
-                self.cpp = ext.ServeSlot(self.pipe.w, batch, self.host_out,
-                                         parts)
-            # one warm-up pass primes the hipBLASLt workspace/algo cache for
-            # the slot stream so submit() never allocates
-            warm = torch.zeros((batch, C.WINDOW_ROWS, C.WINDOW_COLS),
-                               dtype=torch.uint8, device=dev)
-            self.cpp.run(warm, batch)
-            self.cpp.sync()
-            return
-        self.stream = torch.cuda.Stream(device=dev)
-        self.x = torch.zeros(
-            (batch, C.WINDOW_ROWS, C.WINDOW_COLS), dtype=torch.uint8,
-            device=dev
-        )
-        self.event = torch.cuda.Event()
-        with torch.cuda.stream(self.stream):
-            self.amax = pipe._forward_amax(self.x)  # warm-up + output buffer
-            self.host_out.copy_(self.amax, non_blocking=True)
-        self.stream.synchronize()
-        if pipe.use_graphs:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self.stream):
-                self.amax = pipe._forward_amax(self.x)
-                # pinned D2H is capture-legal: folding it into the graph
-                # saves one host call per submitted batch
-                self.host_out.copy_(self.amax, non_blocking=True)
-            self.graph = g
+        self.cpp = _ext().ServeSlot(pipe.w, batch, self.host_out, parts,
+                                    pipe.quality)
+        # one warm-up pass primes the hipBLASLt workspace/algo cache for
+        # the slot stream so submit() never allocates
+        warm = torch.zeros((batch, C.WINDOW_ROWS, C.WINDOW_COLS),
+                           dtype=torch.uint8, device=dev)
+        self.cpp.run(warm, batch)
+        self.cpp.sync()
 
     def wait_done(self):
-        if self.cpp is not None:
-            self.cpp.sync()
-        else:
-            self.event.synchronize()
+        self.cpp.sync()
 
     def unlaunched(self) -> int:
         return self.cpp.unlaunched() if self.parts > 1 else 0
@@ -411,10 +360,6 @@ class _Slot:
             self.launches += 1
 
     def votes_staging(self):
-        if self.cpp is None:
-            raise RuntimeError(
-                "votes mode needs the C++ serving slot (ext.ServeSlot); it is "
-                "not available with ROKO_SERVE=graph or use_graphs=False")
         if self.pending[0] is not None:
             self.pending[0].materialize()
             self.pending[0] = None
@@ -437,10 +382,6 @@ class _Slot:
 
     def submit_votes_device(self, x, pos, n: int, table, n_slots: int,
                             err_flag, qsum=None):
-        if self.cpp is None:
-            raise RuntimeError(
-                "votes mode needs the C++ serving slot (ext.ServeSlot); it is "
-                "not available with ROKO_SERVE=graph or use_graphs=False")
         if x.dtype != torch.uint8 or pos.dtype != torch.int32:
             raise ValueError("x must be uint8 and pos int32")
         if self.pending[0] is not None:
@@ -471,56 +412,12 @@ class _Slot:
             if copy_out:
                 self.pending[part] = t
             return t
-        if self.cpp is not None:
-            # ONE C++ call enqueues the whole forward (GIL released). No
-            # event sync in the hot path: stream ordering makes buffer
-            # reuse safe, tickets sync in materialize(), and
-            # hipEventSynchronize itself measured ~80 us with ~32 live
-            # streams (profiles/PERF_HISTORY.md)
-            self.cpp.submit(x if x.is_contiguous() else x.contiguous(), n)
-            t = _Ticket(self, n)
-            if copy_out:
-                self.pending[0] = t
-            return t
-        self.event.synchronize()  # previous tenant fully drained
-        # the input may have been produced on another stream (usually the
-        # default one): order the slot stream behind it before copying
-        self.stream.wait_stream(torch.cuda.current_stream())
-        if x.is_cuda:
-            # x may be the dtype/contiguity temp created above, freed as soon
-            # as submit() returns — keep its memory until the copy runs
-            x.record_stream(self.stream)
-        with torch.cuda.stream(self.stream):
-            self.x[:n].copy_(x, non_blocking=True)
-            if self.graph is not None:
-                self.graph.replay()  # forward + pinned D2H
-            else:
-                self.amax = self.pipe._forward_amax(self.x)
-                self.host_out.copy_(self.amax, non_blocking=True)
-            self.event.record(self.stream)
+        # ONE C++ call enqueues the whole forward (GIL released). No event
+        # sync in the hot path: stream ordering makes buffer reuse safe,
+        # tickets sync in materialize(), and hipEventSynchronize itself
+        # measured ~80 us with ~32 live streams (profiles/PERF_HISTORY.md)
+        self.cpp.submit(x if x.is_contiguous() else x.contiguous(), n)
         t = _Ticket(self, n)
         if copy_out:
             self.pending[0] = t
         return t
-
-
-def roko_argmax(model, x: torch.Tensor) -> torch.Tensor:
-    """ids -> per-position class predictions (B, 90) uint8, argmax fused."""
-    ext = _ext()
-    w = _bf16_weights(model)
-    B0 = x.shape[0]
-    ids = x.to(torch.uint8).contiguous()
-    pad = (-B0) % 32
-    if pad:
-        ids = torch.cat([ids, ids.new_zeros(pad, *ids.shape[1:])])
-    B = ids.shape[0]
-    T = C.WINDOW_COLS
-    seq = _front_eval(ext, ids, w)
-    for l in range(C.NUM_LAYERS):
-        xg = torch.addmm(
-            w[f"b_ih{l}"], seq.reshape(T * B, -1), w[f"w_ih_t{l}"]
-        ).view(T, B, 2, 384)
-        (hseq,) = ext.gru_layer_fwd(xg.contiguous(), w[f"u{l}"], w[f"bhh{l}"], False)
-        seq = hseq.view(T, B, 2 * C.HIDDEN_SIZE)
-    (amax,) = ext.head_fwd(seq, w["w4"], w["b4"], False, True)
-    return amax[:B0]

@@ -6,6 +6,7 @@
 
 #include <cstdint>
 
+#include "api.h"
 #include "common.h"
 
 namespace rk {

@@ -28,6 +28,7 @@
 
 #include <cstdint>
 
+#include "api.h"
 #include "common.h"
 #include "votes.h"
 

@@ -27,6 +27,7 @@
 
 #include <cstdint>
 
+#include "api.h"
 #include "common.h"
 
 namespace rk {

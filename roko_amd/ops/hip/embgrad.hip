@@ -13,6 +13,7 @@
 
 #include <cstdint>
 
+#include "api.h"
 #include "common.h"
 
 namespace rk {

@@ -35,6 +35,7 @@
 
 #include <cstdint>
 
+#include "api.h"
 #include "common.h"
 
 namespace rk {

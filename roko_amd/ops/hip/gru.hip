@@ -48,6 +48,7 @@
 #include <string>
 #include <type_traits>
 
+#include "api.h"
 #include "common.h"
 
 namespace rk {
@@ -731,6 +732,25 @@ static void launch_eval2(const bf16* xg, const bf16* u, const float* bhh,
 #undef RK_E2
 }
 
+// ROKO_GRU_EVAL=v1: the old eval kernels, process-wide
+static bool env_gru_eval_v1() {
+    static const bool v = [] {
+        const char* f = getenv("ROKO_GRU_EVAL");
+        return f && std::string(f) == "v1";
+    }();
+    return v;
+}
+
+// ROKO_GRU_MB=32: the 32-row tile in the training forward, the old eval
+// kernels and the backward, process-wide
+static bool env_gru_mb32() {
+    static const bool v = [] {
+        const char* f = getenv("ROKO_GRU_MB");
+        return f && std::string(f) == "32";
+    }();
+    return v;
+}
+
 // Which eval kernel a gru_layer_fwd(cache == nullptr) call launches:
 // 1 the old kernels, 2 the transposed kernel; for the timing script only, 3
 // the transposed kernel with the hseq store variant that is not shipped and
@@ -738,14 +758,7 @@ static void launch_eval2(const bf16* xg, const bf16* u, const float* bhh,
 // impl: 0 default (the transposed kernel; ROKO_GRU_EVAL=v1 or ROKO_GRU_MB=32
 // make that the old kernels, process-wide), 1/2/3 as above.
 int gru_eval_select(int impl, int B) {
-    static const bool eval_v1 = [] {
-        const char* f = getenv("ROKO_GRU_EVAL");
-        return f && std::string(f) == "v1";
-    }();
-    static const bool mb32 = [] {
-        const char* f = getenv("ROKO_GRU_MB");
-        return f && std::string(f) == "32";
-    }();
+    const bool eval_v1 = env_gru_eval_v1(), mb32 = env_gru_mb32();
     if (impl < 0 || impl > 4)
         throw std::invalid_argument("gru_layer_fwd: impl must be 0..4");
     if (impl >= 2 && (B % 16) != 0)
@@ -793,10 +806,7 @@ void gru_layer_fwd(const void* xg, const void* u, const float* bhh, void* hseq,
     // at the 2-wave VALU-issue floor, so the wall nearly halves (eval
     // 175.6 -> 97.7 us measured) and the WG count doubles (serving
     // packing). ROKO_GRU_MB=32 reverts both paths.
-    static const int mb_sel = [] {
-        const char* f = getenv("ROKO_GRU_MB");
-        return (f && std::string(f) == "32") ? 32 : 16;
-    }();
+    const int mb_sel = env_gru_mb32() ? 32 : 16;
     if (cache) {
         if (mb_sel == 16 && (B % 16) == 0)
             hipLaunchKernelGGL((gru_layer_fwd_kernel<true, 0, 16>),
@@ -817,12 +827,8 @@ void gru_layer_fwd(const void* xg, const void* u, const float* bhh, void* hseq,
     else {
         // eval tile choice: MBT=16 doubles the WG count and halves each
         // thread's gate-chain count (ROKO_GRU_MB=32 reverts)
-        static const int mb_eval = [] {
-            const char* f = getenv("ROKO_GRU_MB");
-            return (f && std::string(f) == "32") ? 32 : 16;
-        }();
         // (a batch that is a multiple of 16 only has no 32-row form)
-        if ((mb_eval == 16 || (B % 32) != 0) && (B % 16) == 0)
+        if ((mb_sel == 16 || (B % 32) != 0) && (B % 16) == 0)
             hipLaunchKernelGGL((gru_layer_fwd_kernel<false, 0, 16>),
                                dim3(B / 16, 2), block, 0, stream,
                                static_cast<const bf16*>(xg),
@@ -1126,10 +1132,7 @@ void gru_layer_bwd(const void* cache, const void* hseq, const void* dhin,
                    const void* ut, void* dxg, void* dhg, int T, int B,
                    hipStream_t stream, uint32_t dbg) {
     dim3 block(BW_WAVES * 64);
-    static const int mb_sel = [] {
-        const char* f = getenv("ROKO_GRU_MB");
-        return (f && std::string(f) == "32") ? 32 : 16;
-    }();
+    const int mb_sel = env_gru_mb32() ? 32 : 16;
     if (mb_sel == 16 && (B % 16) == 0)
         hipLaunchKernelGGL((gru_layer_bwd_kernel<16>), dim3(B / 16, 2), block,
                            0, stream, static_cast<const bf16*>(cache),

@@ -4,6 +4,7 @@
 // before anything else trusts them (cdna_hip_programming.md §3: always
 // verify with ASYMMETRIC operands).
 
+#include "api.h"
 #include "common.h"
 
 namespace rk {

@@ -12,6 +12,7 @@
 
 #include <cstdint>
 
+#include "api.h"
 #include "common.h"
 #include "votes.h"  // table formats, vote_majority, vote_quality
 

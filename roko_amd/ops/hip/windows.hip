@@ -47,6 +47,7 @@
 
 #include <cstdint>
 
+#include "api.h"
 #include "common.h"
 
 namespace rk {

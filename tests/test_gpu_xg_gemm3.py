@@ -119,14 +119,17 @@ def test_front_leading_dimension():
 @requires_gpu
 def test_switch_parity(monkeypatch):
     """ROKO_XG3=0 (xg_gemm2, 500-stride front output) and the default
-    (xg_gemm3, 512-stride) serve identical predictions."""
+    (xg_gemm3, 512-stride) serve identical predictions, and the slot's plan
+    shows that the switch did select the other kernel."""
     from roko_amd.ops.forward import InferencePipeline
+    from tests.serve_plan_cases import expected_plan
 
     torch.manual_seed(9)
     model = RokoModel().cuda().eval()
     g = torch.Generator().manual_seed(13)
     x = torch.randint(0, 12, (128, 200, 90), generator=g,
                       dtype=torch.uint8).cuda()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
     preds = []
     for flag in ("0", None):
         if flag is None:
@@ -134,6 +137,12 @@ def test_switch_parity(monkeypatch):
         else:
             monkeypatch.setenv("ROKO_XG3", flag)
         pipe = InferencePipeline(model, 128, depth=1)
+        plan = pipe.slots[0].cpp.plan
+        if flag == "0":
+            assert plan["xg"] == ["xg2"] * 3 and plan["seq_ld"] == 500
+        else:
+            assert plan["xg"][0] == "xg3" and plan["seq_ld"] == 512
+            assert plan["xg"] == expected_plan(128, cus)["xg"]
         preds.append(pipe.submit(x, copy_out=True)().clone())
         del pipe
     assert preds[0].shape == (128, 90)

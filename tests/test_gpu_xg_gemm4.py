@@ -6,6 +6,7 @@ comparison here is bitwise against xg_gemm3, into sentinel-filled outputs,
 at the smallest shapes where the walk, the XCD placement and the tile
 boundary can go wrong."""
 
+import json
 import os
 import subprocess
 import sys
@@ -13,6 +14,8 @@ import sys
 import numpy as np
 import pytest
 import torch
+
+from tests.serve_plan_cases import expected_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -192,6 +195,7 @@ def test_schedule_screen(kreal, kp, form):
 
 
 _CHILD = r"""
+import json
 import sys
 sys.path.insert(0, sys.argv[1])
 import numpy as np
@@ -205,6 +209,7 @@ xs = [torch.randint(0, 12, (128, 200, 90), generator=g,
                     dtype=torch.uint8).cuda() for _ in range(2)]
 pipe = InferencePipeline(model, 128, depth=2, coalesce=2)
 assert pipe.coalesce == 2 and len(pipe.slots) == 1
+print("plan", json.dumps(pipe.slots[0].cpp.plan))
 tickets = [pipe.submit(x, copy_out=True) for x in xs]
 preds = torch.stack([t().clone() for t in tickets])
 assert preds.shape == (2, 128, 90)
@@ -235,11 +240,20 @@ def test_switch_parity(tmp_path):
         procs.append((path, subprocess.Popen(
             [sys.executable, "-c", _CHILD, ROOT, path], env=env,
             stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
+    # what each child's slot (width 256) must have chosen, so that equal
+    # predictions mean different kernels agreed
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    want = {"0": ["xg3"] * 3, "stream": ["stream"] * 3,
+            "wstat": ["xg3", "wstat", "wstat"],
+            None: expected_plan(256, cus)["xg"]}
     preds = []
-    for path, proc in procs:
+    for flag, (path, proc) in zip(flags, procs):
         stdout, stderr = proc.communicate(timeout=300)
         assert proc.returncode == 0, stderr[-2000:]
         assert "child ok" in stdout
+        plan = json.loads(next(l for l in stdout.splitlines()
+                               if l.startswith("plan "))[5:])
+        assert plan["xg"] == want[flag], (flag, plan)
         preds.append(np.load(path))
     assert preds[0].shape == (2, 128, 90)
     assert np.array_equal(preds[0], preds[1])
