@@ -12,6 +12,7 @@
 #include "align.h"
 #include "bam.h"
 #include "pileup.h"
+#include "wfa.h"
 
 namespace py = pybind11;
 
@@ -158,4 +159,40 @@ PYBIND11_MODULE(_pileup, m) {
         },
         py::arg("query"), py::arg("target"), py::arg("band") = 128,
         "align_stats plus the M/I/D CIGAR of query against target");
+    m.def(
+        "wfa_ops",
+        [](const std::string& query, const std::string& target,
+           int64_t max_score) {
+            std::string ops;
+            {
+                py::gil_scoped_release release;
+                ops = rk::wfa_ops(query, target, max_score);
+            }
+            return py::bytes(ops);
+        },
+        py::arg("query"), py::arg("target"), py::arg("max_score") = -1,
+        "Exact wavefront alignment: the X/D/I op string (contract: wfa.py)");
+    m.def(
+        "replay_ops",
+        [](const std::string& query, const std::string& target,
+           const std::string& ops) {
+            rk::AlignStats s;
+            std::string cig;
+            try {
+                py::gil_scoped_release release;
+                s = rk::replay_ops(query, target, ops, &cig);
+            } catch (const std::invalid_argument& e) {
+                throw py::value_error(e.what());
+            }
+            py::dict d;
+            d["edit_distance"] = s.edit_distance;
+            d["matches"] = s.matches;
+            d["mismatches"] = s.mismatches;
+            d["insertions"] = s.insertions;
+            d["deletions"] = s.deletions;
+            d["cigar"] = cig;
+            return d;
+        },
+        py::arg("query"), py::arg("target"), py::arg("ops"),
+        "Counts and CIGAR of an op string; ValueError if it does not replay");
 }

@@ -149,4 +149,12 @@ void gather_batch(const uint8_t* X, const uint8_t* Y, const int32_t* idx,
 void eval_metrics(const float* logits, const uint8_t* labels, int64_t n,
                   double inv_n, uint64_t* correct, double* loss_sum,
                   hipStream_t stream);
+int wfa_probe();
+int wfa_coop();
+int wfa_pad();
+int64_t wfa_dir_cells(int64_t n, int64_t m, int64_t s0, int64_t s1);
+void wfa_steps(const uint8_t* q, const uint8_t* t, int n, int m, int s0,
+               int s1, int* offs, uint8_t* dir, int* done, hipStream_t stream);
+void wfa_trace(const uint8_t* dir, int n, int m, int s0, int s_hi, int* walk,
+               uint8_t* ops, hipStream_t stream);
 }  // namespace rk

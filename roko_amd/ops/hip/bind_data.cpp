@@ -411,6 +411,65 @@ void eval_metrics(torch::Tensor logits, torch::Tensor labels, double inv_n,
     check_launch("eval_metrics kernel");
 }
 
+// ---------------------------------------------------------------------------
+// Wavefront aligner (wfa.hip; contract and driver: roko_amd/wfa.py). `q` and
+// `t` carry wfa_pad() pad bytes after their n and m sequence bytes, `offs` is
+// the two offset rows (2, n + m + 3) int32, `done` one int32 (-1 until the
+// end cell is reached, then the edit distance).
+void wfa_check_seqs(const torch::Tensor& q, const torch::Tensor& t, int64_t n,
+                    int64_t m) {
+    check(q, torch::kUInt8, "q");
+    check(t, torch::kUInt8, "t");
+    TORCH_CHECK(n >= 0 && m >= 0 && n + m + 3 + rk::wfa_pad() < (int64_t(1) << 31),
+                "sequence lengths out of range");
+    TORCH_CHECK(q.numel() == n + rk::wfa_pad() && t.numel() == m + rk::wfa_pad(),
+                "q and t must hold the sequence plus wfa_pad() bytes");
+}
+
+// scores [s0, s1) of one chunk, one launch each; `dir` is the chunk's
+// direction table of exactly wfa_dir_cells(n, m, s0, s1) bytes
+void wfa_steps(torch::Tensor q, torch::Tensor t, int64_t n, int64_t m,
+               int64_t s0, int64_t s1, torch::Tensor offs, torch::Tensor dir,
+               torch::Tensor done) {
+    wfa_check_seqs(q, t, n, m);
+    check(offs, torch::kInt32, "offs");
+    check(dir, torch::kUInt8, "dir");
+    check(done, torch::kInt32, "done");
+    TORCH_CHECK(0 <= s0 && s0 < s1 && s1 <= std::max(n, m) + 1,
+                "score range out of bounds");
+    TORCH_CHECK(offs.numel() == 2 * (n + m + 3), "offs must be (2, n + m + 3)");
+    TORCH_CHECK(dir.numel() == rk::wfa_dir_cells(n, m, s0, s1),
+                "dir must hold wfa_dir_cells(n, m, s0, s1) bytes");
+    TORCH_CHECK(done.numel() == 1, "done must hold one int32");
+    const c10::cuda::CUDAGuard guard(q.device());
+    rk::wfa_steps(q.data_ptr<uint8_t>(), t.data_ptr<uint8_t>(), (int)n, (int)m,
+                  (int)s0, (int)s1, offs.data_ptr<int32_t>(),
+                  dir.data_ptr<uint8_t>(), done.data_ptr<int32_t>(),
+                  cur_stream());
+    check_launch("wfa step kernel");
+}
+
+// one chunk of the traceback: scores s_hi down to max(s0, 1) of the table
+// that starts at score s0; walk = {diagonal, error flag}
+void wfa_trace(torch::Tensor dir, int64_t n, int64_t m, int64_t s0,
+               int64_t s_hi, torch::Tensor walk, torch::Tensor ops) {
+    check(dir, torch::kUInt8, "dir");
+    check(walk, torch::kInt32, "walk");
+    check(ops, torch::kUInt8, "ops");
+    TORCH_CHECK(n >= 0 && m >= 0 && n + m + 3 < (int64_t(1) << 31),
+                "sequence lengths out of range");
+    TORCH_CHECK(0 <= s0 && s0 <= s_hi && 1 <= s_hi && s_hi <= ops.numel(),
+                "score range out of bounds");
+    TORCH_CHECK(dir.numel() >= rk::wfa_dir_cells(n, m, s0, s_hi + 1),
+                "dir does not reach score s_hi");
+    TORCH_CHECK(walk.numel() == 2, "walk must hold two int32");
+    const c10::cuda::CUDAGuard guard(dir.device());
+    rk::wfa_trace(dir.data_ptr<uint8_t>(), (int)n, (int)m, (int)s0, (int)s_hi,
+                  walk.data_ptr<int32_t>(), ops.data_ptr<uint8_t>(),
+                  cur_stream());
+    check_launch("wfa trace kernel");
+}
+
 }  // namespace
 
 void bind_data(py::module_& m) {
@@ -449,4 +508,14 @@ void bind_data(py::module_& m) {
           py::arg("idx"), py::arg("out_x"), py::arg("out_y"));
     m.def("eval_metrics", &eval_metrics, py::arg("logits"), py::arg("labels"),
           py::arg("inv_n"), py::arg("acc"));
+    m.def("wfa_probe", &rk::wfa_probe);
+    m.def("wfa_coop", &rk::wfa_coop);
+    m.def("wfa_pad", &rk::wfa_pad);
+    m.def("wfa_dir_cells", &rk::wfa_dir_cells, py::arg("n"), py::arg("m"),
+          py::arg("s0"), py::arg("s1"));
+    m.def("wfa_steps", &wfa_steps, py::arg("q"), py::arg("t"), py::arg("n"),
+          py::arg("m"), py::arg("s0"), py::arg("s1"), py::arg("offs"),
+          py::arg("dir"), py::arg("done"));
+    m.def("wfa_trace", &wfa_trace, py::arg("dir"), py::arg("n"), py::arg("m"),
+          py::arg("s0"), py::arg("s_hi"), py::arg("walk"), py::arg("ops"));
 }
