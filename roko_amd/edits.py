@@ -204,15 +204,17 @@ VCF_COLUMNS = "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO"
 
 
 def write_vcf(path: str, contig_lens: Sequence[Tuple[str, int]],
-              records: Iterable[VcfRecord]) -> int:
+              records: Iterable[VcfRecord],
+              extra_header: Sequence[str] = ()) -> int:
     """Write VCF 4.2: one ##contig line per (name, length) of `contig_lens`
-    in the given order, then `records` as they come. Returns the number of
-    records. Creates parent dirs."""
+    in the given order, then `records` as they come. `extra_header` lines
+    (stitch.filter_header) follow ##source. Returns the number of records.
+    Creates parent dirs."""
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
     n = 0
     with open(path, "w") as fh:
-        for line in VCF_HEADER:
+        for line in tuple(VCF_HEADER) + tuple(extra_header):
             fh.write(line + "\n")
         for name, length in contig_lens:
             fh.write(f"##contig=<ID={name},length={length}>\n")

@@ -182,12 +182,16 @@ def stitch_dense(draft: str, maj: np.ndarray) -> str:
 
 
 def _infer_device_votes(rkw, dl, model, batch_size, depth, meter,
-                        quality=False, edits=None):
+                        quality=False, edits=None, min_qual=0,
+                        keep_uncovered=False, stitch="host"):
     """RKW windows -> DeviceVotes: predictions and vote tables stay on the
     GPU; returns ({contig: polished}, windows, {contig: quality string} or
     None). Positions are fetched per batch from the mmap in runs of one
     window group. With a dict `edits` (needs quality) every voted contig's
-    edits (roko_amd/edits.py), compacted on the device, are put into it."""
+    edits (roko_amd/edits.py), compacted on the device, are put into it.
+    `min_qual` and `keep_uncovered` (not at their defaults: needs quality)
+    filter the stitch and the edits (roko_amd/stitch.py); stitch="device"
+    writes the sequences on the GPU (DeviceVotes.stitch)."""
     from .ops.forward import InferencePipeline
     from .ops.votes import DeviceVotes
 
@@ -229,13 +233,29 @@ def _infer_device_votes(rkw, dl, model, batch_size, depth, meter,
         draft = rkw.contig_seq(name)
         if not dv.has_votes(name):
             out[name] = draft
+            continue
+        if edits is not None:
+            from .stitch import applied_edits
+
+            edits[name] = applied_edits(dv.edits(name, draft), min_qual,
+                                        keep_uncovered)
+        if stitch == "device":
+            out[name], qual = dv.stitch(name, draft, min_qual,
+                                        keep_uncovered)
+            if quality:
+                quals[name] = qual
+            dv.free(name)
         elif quality:
             from .quality import stitch_dense_qual
+            from .stitch import is_default, stitch_filtered
 
-            if edits is not None:
-                edits[name] = dv.edits(name, draft)
-            out[name], quals[name] = stitch_dense_qual(
-                draft, *dv.consensus_quality(name))
+            if is_default(min_qual, keep_uncovered):
+                out[name], quals[name] = stitch_dense_qual(
+                    draft, *dv.consensus_quality(name))
+            else:
+                out[name], quals[name] = stitch_filtered(
+                    draft, *dv.consensus_quality(name), min_qual,
+                    keep_uncovered)
             dv.free(name)
         else:
             out[name] = stitch_dense(draft, dv.consensus(name))
@@ -246,12 +266,13 @@ def _infer_device_votes(rkw, dl, model, batch_size, depth, meter,
 def _write_outputs(out: Dict[str, str], quals: Optional[Dict[str, str]],
                    out_path: Optional[str], out_fastq: Optional[str],
                    log, out_vcf: Optional[str] = None, refs=None,
-                   edits=None) -> None:
+                   edits=None, vcf_header=()) -> None:
     """FASTA and/or FASTQ of the polished contigs, sorted by name. A contig
     without an entry in `quals` came through as draft: all Q0. With
     `out_vcf`, the VCF of `edits` ({contig: edits.EDIT_DTYPE array}) over
     `refs` ((name, draft) pairs in the draft's order); a contig without an
-    entry has no records, only its ##contig line."""
+    entry has no records, only its ##contig line; `vcf_header` lines
+    (stitch.vcf_header) go into its header."""
     if out_path:
         write_fasta(out_path, sorted(out.items()))
         log(f"wrote {len(out)} polished contigs to {out_path}")
@@ -267,7 +288,7 @@ def _write_outputs(out: Dict[str, str], quals: Optional[Dict[str, str]],
         from .edits import contig_vcf_records, write_vcf
 
         n = write_vcf(out_vcf, [(name, len(seq)) for name, seq in refs],
-                      contig_vcf_records(refs, edits))
+                      contig_vcf_records(refs, edits), vcf_header)
         log(f"wrote {n} records of "
             f"{sum(len(e) for e in edits.values())} edits to {out_vcf}")
 
@@ -285,6 +306,9 @@ def infer(
     depth: int = 48,
     out_fastq: Optional[str] = None,
     out_vcf: Optional[str] = None,
+    min_qual: int = 0,
+    keep_uncovered: bool = False,
+    stitch: str = "host",
 ) -> Dict[str, str]:
     """Polish the draft in `data_path` (RKW inference file) and return
     {contig: polished sequence}. Writes FASTA if `out_path` is given.
@@ -307,10 +331,32 @@ def infer(
     polished sequence (roko_amd/edits.py), under the rules of `out_fastq`:
     single process; on a GPU the edits are compacted on the device from the
     vote tables and need votes="device"; on the CPU the numpy reference runs.
+
+    `min_qual` (0..60) applies only the edits of at least that quality and
+    `keep_uncovered` keeps draft bases no window covered (roko_amd/
+    stitch.py). Either turns the quality tables on and falls under the rules
+    of `out_fastq`; the VCF then lists only the applied edits.
+    `stitch="device"` writes the polished sequences on the GPU
+    (DeviceVotes.stitch): it needs a GPU and votes="device" (or votes unset).
     """
+    from .stitch import check_filter, is_default, vcf_header
+
     if votes not in (None, "host", "device"):
         raise ValueError(f"votes must be 'host' or 'device', got {votes!r}")
+    if stitch not in ("host", "device"):
+        raise ValueError(f"stitch must be 'host' or 'device', got {stitch!r}")
+    min_qual, keep_uncovered = check_filter(min_qual, keep_uncovered)
+    filtered = not is_default(min_qual, keep_uncovered)
     rank, local_rank, world = init_distributed()
+    if min_qual > 0 and world > 1:
+        raise ValueError("min_qual is single-process only "
+                         f"(WORLD_SIZE={world}); run one process")
+    if keep_uncovered and world > 1:
+        raise ValueError("keep_uncovered is single-process only "
+                         f"(WORLD_SIZE={world}); run one process")
+    if stitch == "device" and world > 1:
+        raise ValueError("stitch='device' is single-process only "
+                         f"(WORLD_SIZE={world}); use stitch='host'")
     if out_fastq and world > 1:
         raise ValueError("out_fastq is single-process only "
                          f"(WORLD_SIZE={world}); run one process")
@@ -327,17 +373,31 @@ def infer(
             else torch.device("cpu")
         )
     device = torch.device(device)
-    if (out_fastq or out_vcf) and device.type == "cuda":
-        if votes == "host":
+    if stitch == "device":
+        if device.type != "cuda":
             raise ValueError(
-                f"{'out_fastq' if out_fastq else 'out_vcf'} on a GPU "
+                "stitch='device' writes the polished sequence on the GPU "
+                f"and needs a GPU device (got {device.type!r}); use "
+                "stitch='host'")
+        if votes == "host":
+            raise ValueError("stitch='device' reads the device vote tables "
+                             "and needs votes='device' (or leave votes "
+                             "unset)")
+        votes = "device"
+    if (out_fastq or out_vcf or filtered) and device.type == "cuda":
+        if votes == "host":
+            what = ("out_fastq" if out_fastq else "out_vcf" if out_vcf
+                    else "min_qual" if min_qual > 0 else "keep_uncovered")
+            raise ValueError(
+                f"{what} on a GPU "
                 "computes the qualities on the device "
                 "and needs votes='device' (or leave votes unset)")
         votes = "device"
     if votes is None:
         votes = "host"
-    # the edits carry qualities, so a VCF turns the quality tables on
-    quality = bool(out_fastq or out_vcf)
+    # the edits carry qualities, so a VCF turns the quality tables on; so
+    # does a filter not at its defaults, which is decided per slot from them
+    quality = bool(out_fastq or out_vcf or filtered)
     edits: Optional[Dict[str, np.ndarray]] = {} if out_vcf else None
 
     if model is None:
@@ -357,6 +417,7 @@ def infer(
     # streaming per-contig vote accumulation (bounded memory)
     if quality:
         from .quality import StreamingQualityVotes, phred_units, stitch_tables
+        from .stitch import applied_edits, stitch_tables_filtered
 
         sv = StreamingQualityVotes()
     else:
@@ -384,7 +445,8 @@ def infer(
     with torch.no_grad():
         if votes == "device":
             out, n_windows, quals = _infer_device_votes(
-                rkw, dl, model, batch_size, depth, meter, quality, edits)
+                rkw, dl, model, batch_size, depth, meter, quality, edits,
+                min_qual, keep_uncovered, stitch)
         elif pipe is not None:
             # pipelined: keep `depth` batches in flight; votes are harvested
             # one pipeline-depth behind submission
@@ -422,7 +484,7 @@ def infer(
         if out_vcf else None
     if out is not None:
         _write_outputs(out, quals, out_path, out_fastq, log, out_vcf, refs,
-                       edits)
+                       edits, vcf_header(min_qual, keep_uncovered))
         return out
 
     if quality:
@@ -447,7 +509,10 @@ def infer(
     quals = {}
     for name in rkw.contig_names():
         draft = rkw.contig_seq(name)
-        if name in tables:
+        if name in tables and filtered:
+            out[name], quals[name] = stitch_tables_filtered(
+                draft, tables[name], sums[name], min_qual, keep_uncovered)
+        elif name in tables:
             out[name] = stitch_contig(draft, *tables[name])
             if quality:
                 seq, quals[name] = stitch_tables(draft, tables[name],
@@ -456,14 +521,16 @@ def infer(
                     raise RuntimeError(
                         f"{name}: the quality stitch disagrees with the "
                         "sequence stitch")
-                if edits is not None:
-                    from .edits import table_edits
-
-                    edits[name] = table_edits(draft, tables[name],
-                                              sums[name])
         else:
             out[name] = draft
-    _write_outputs(out, quals, out_path, out_fastq, log, out_vcf, refs, edits)
+        if name in tables and edits is not None:
+            from .edits import table_edits
+
+            edits[name] = applied_edits(
+                table_edits(draft, tables[name], sums[name]), min_qual,
+                keep_uncovered)
+    _write_outputs(out, quals, out_path, out_fastq, log, out_vcf, refs, edits,
+                   vcf_header(min_qual, keep_uncovered))
     return out
 
 
@@ -482,9 +549,23 @@ def main(argv=None):
                    help="also write VCF: the edits between the draft and "
                         "the polished sequence (single process; on a GPU "
                         "the votes run on the device)")
+    p.add_argument("--min-qual", type=int, default=0, metavar="Q",
+                   help="apply only edits of quality Q or more (0..60); a "
+                        "rejected edit leaves the draft as it was, at Q0 "
+                        "(single process; on a GPU the votes run on the "
+                        "device)")
+    p.add_argument("--keep-uncovered", action="store_true",
+                   help="keep draft bases inside the polished span that no "
+                        "window covered (Q0) instead of dropping them "
+                        "(single process)")
+    p.add_argument("--stitch", choices=("host", "device"), default="host",
+                   help="where the polished sequence is put together: numpy "
+                        "over the fetched consensus (host) or the GPU, from "
+                        "the device vote tables (device)")
     a = p.parse_args(argv)
     infer(a.data, a.model, a.out, batch_size=a.b, workers=a.t,
-          out_fastq=a.fastq, out_vcf=a.vcf)
+          out_fastq=a.fastq, out_vcf=a.vcf, min_qual=a.min_qual,
+          keep_uncovered=a.keep_uncovered, stitch=a.stitch)
 
 
 if __name__ == "__main__":

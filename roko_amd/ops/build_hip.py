@@ -25,7 +25,7 @@ def build():
              "bind_data.cpp", "serve_slot.cpp",
              "adam.hip", "batch.hip", "ce.hip", "edits.hip", "embed_mlp.hip",
              "embgrad.hip", "front_train.hip", "gemm.hip", "gru.hip",
-             "head.hip", "probe.hip", "votes.hip", "wfa.hip", "windows.hip"]
+             "head.hip", "probe.hip", "stitch.hip", "votes.hip", "wfa.hip", "windows.hip"]
     sources = [os.path.join(HERE, "hip", n) for n in names]
     load(
         name="_hip_ops",

@@ -107,12 +107,25 @@ void vote_consensus_q(const uint32_t* table, const uint64_t* qsum,
                       int64_t n_slots, uint8_t* maj, uint8_t* qual,
                       hipStream_t stream);
 int64_t edit_num_blocks(int64_t n_pos);
+void edit_bounds(const uint32_t* table, int64_t n_pos, int64_t* state,
+                 hipStream_t stream);
+void edit_scan(int64_t* counts, int64_t n, int64_t* state,
+               hipStream_t stream);
 void edit_count(const uint32_t* table, const uint8_t* draft, int64_t n_pos,
                 int64_t* state, int64_t* counts, hipStream_t stream);
 void edit_write(const uint32_t* table, const uint64_t* qsum,
                 const uint8_t* draft, int64_t n_pos, const int64_t* state,
                 const int64_t* offsets, void* records, int64_t total,
                 hipStream_t stream);
+void stitch_count(const uint32_t* table, const uint64_t* qsum,
+                  const uint8_t* draft, int64_t n_pos, int64_t* state,
+                  int64_t* counts, int min_qual, bool keep_uncovered,
+                  hipStream_t stream);
+void stitch_write(const uint32_t* table, const uint64_t* qsum,
+                  const uint8_t* draft, int64_t n_pos, const int64_t* state,
+                  const int64_t* offsets, int min_qual, bool keep_uncovered,
+                  uint8_t* seq, uint8_t* qual, int64_t total,
+                  hipStream_t stream);
 bool windows_geometry_ok(int rows, int cols, int stride, int max_ins);
 void windows_index(const int32_t* ref_start, const int32_t* ref_end,
                    const uint8_t* reverse, const uint32_t* cigar_off,

@@ -1,4 +1,4 @@
-// Bindings of the data kernels: votes, edits, windows, truth labels, batch
+// Bindings of the data kernels: votes, edits, stitch, windows, truth labels, batch
 // gather and eval metrics.
 
 #include <c10/cuda/CUDAGuard.h>
@@ -145,6 +145,69 @@ void edit_write(torch::Tensor table, torch::Tensor qsum, torch::Tensor draft,
                    edit_counts_ptr(offsets, n_pos), records.data_ptr(), total,
                    cur_stream());
     check_launch("edit kernel");
+}
+
+// ---------------------------------------------------------------------------
+// Device stitch (stitch.hip): the polished sequence and its quality string
+// under the quality filter. `state` and `counts` are those of the edit
+// kernels; `qsum` may be None (tables built without quality), and then
+// min_qual is 0 and no quality string can be asked for.
+const uint64_t* stitch_qsum_ptr(const c10::optional<torch::Tensor>& qsum,
+                                int64_t n_slots, int64_t min_qual) {
+    TORCH_CHECK(min_qual >= 0 && min_qual <= 60, "min_qual outside 0..60");
+    if (!qsum.has_value()) {
+        TORCH_CHECK(min_qual == 0, "min_qual > 0 needs the quality table");
+        return nullptr;
+    }
+    return vote_qsum_ptr(*qsum, n_slots);
+}
+
+// bounds + bytes per workgroup + their exclusive scan, three kernels
+void stitch_count(torch::Tensor table, c10::optional<torch::Tensor> qsum,
+                  torch::Tensor draft, int64_t n_slots, torch::Tensor state,
+                  torch::Tensor counts, int64_t min_qual,
+                  bool keep_uncovered) {
+    uint32_t* tab = vote_table_ptr(table, n_slots);
+    const uint64_t* qs = stitch_qsum_ptr(qsum, n_slots, min_qual);
+    const uint8_t* dr = edit_draft_ptr(draft, n_slots);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(tab) % 16 == 0,
+                "vote tables must be 16-byte aligned");
+    const int64_t n_pos = draft.numel();
+    rk::stitch_count(tab, qs, dr, n_pos, edit_state_ptr(state),
+                     edit_counts_ptr(counts, n_pos), (int)min_qual,
+                     keep_uncovered, cur_stream());
+    check_launch("stitch kernel");
+}
+
+// the polished bytes, `total` of them (state[2] as read back by the caller),
+// into `seq` and, if given, their Phred+33 qualities into `qual`
+void stitch_write(torch::Tensor table, c10::optional<torch::Tensor> qsum,
+                  torch::Tensor draft, int64_t n_slots, torch::Tensor state,
+                  torch::Tensor offsets, int64_t min_qual, bool keep_uncovered,
+                  torch::Tensor seq, c10::optional<torch::Tensor> qual,
+                  int64_t total) {
+    uint32_t* tab = vote_table_ptr(table, n_slots);
+    const uint64_t* qs = stitch_qsum_ptr(qsum, n_slots, min_qual);
+    const uint8_t* dr = edit_draft_ptr(draft, n_slots);
+    check(seq, torch::kUInt8, "seq");
+    TORCH_CHECK(total >= 0 && seq.numel() == total,
+                "seq must hold one byte per polished base");
+    uint8_t* ql = nullptr;
+    if (qual.has_value()) {
+        TORCH_CHECK(qs != nullptr, "a quality string needs the quality table");
+        check(*qual, torch::kUInt8, "qual");
+        TORCH_CHECK(qual->numel() == total,
+                    "qual must hold one byte per polished base");
+        ql = qual->data_ptr<uint8_t>();
+    }
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(tab) % 16 == 0,
+                "vote tables must be 16-byte aligned");
+    const int64_t n_pos = draft.numel();
+    rk::stitch_write(tab, qs, dr, n_pos, edit_state_ptr(state),
+                     edit_counts_ptr(offsets, n_pos), (int)min_qual,
+                     keep_uncovered, seq.data_ptr<uint8_t>(), ql, total,
+                     cur_stream());
+    check_launch("stitch kernel");
 }
 
 // ---------------------------------------------------------------------------
@@ -490,6 +553,13 @@ void bind_data(py::module_& m) {
     m.def("edit_write", &edit_write, py::arg("table"), py::arg("qsum"),
           py::arg("draft"), py::arg("n_slots"), py::arg("state"),
           py::arg("offsets"), py::arg("records"), py::arg("total"));
+    m.def("stitch_count", &stitch_count, py::arg("table"), py::arg("qsum"),
+          py::arg("draft"), py::arg("n_slots"), py::arg("state"),
+          py::arg("counts"), py::arg("min_qual"), py::arg("keep_uncovered"));
+    m.def("stitch_write", &stitch_write, py::arg("table"), py::arg("qsum"),
+          py::arg("draft"), py::arg("n_slots"), py::arg("state"),
+          py::arg("offsets"), py::arg("min_qual"), py::arg("keep_uncovered"),
+          py::arg("seq"), py::arg("qual"), py::arg("total"));
     m.def("build_windows", &build_windows, py::arg("ref_start"),
           py::arg("ref_end"), py::arg("reverse"), py::arg("cigar_off"),
           py::arg("seq_off"), py::arg("cigar"), py::arg("seq4"),

@@ -30,51 +30,14 @@
 
 #include "api.h"
 #include "common.h"
+#include "edits.h"
 #include "votes.h"
 
 namespace rk {
 
-constexpr int EDIT_TILE = 256;        // positions (threads) per workgroup
-constexpr int EDIT_WAVES = EDIT_TILE / 64;
-constexpr int EDIT_SCAN_THREADS = 1024;
 // the bounds kernel ends in two same-address atomics per workgroup, which
 // the L2 serialises (measured ~12 ns each): a capped grid keeps that constant
 constexpr unsigned EDIT_BOUNDS_BLOCKS = 512;
-constexpr uint32_t EDIT_GAP_CLASS = 4;
-constexpr uint32_t EDIT_GAP_CHAR = '*';
-constexpr uint32_t EDIT_BASE_CHARS = 0x54474341u;  // "ACGT", class c in byte c
-
-RK_DEV uint32_t edit_base_char(uint32_t cls) {
-    return (EDIT_BASE_CHARS >> (8 * cls)) & 0xFFu;
-}
-
-RK_DEV uint32_t edit_upper(uint32_t d) {
-    return (d >= 'a' && d <= 'z') ? d - 32u : d;
-}
-
-// The 4 slots of one position -> bit k set when slot k is an edit; maj4 gets
-// the four majorities, one per byte. `d` is the draft byte, uppercased.
-RK_DEV uint32_t edit_mask(const uint4 v, uint32_t d, bool in_window,
-                          uint32_t* maj4) {
-    const uint32_t m0 = vote_majority(v.x), m1 = vote_majority(v.y),
-                   m2 = vote_majority(v.z), m3 = vote_majority(v.w);
-    *maj4 = m0 | (m1 << 8) | (m2 << 16) | (m3 << 24);
-    if (!in_window) return 0u;
-    // ins == 0: not voted (0xFF), GAP, or a base other than the draft's
-    const uint32_t e0 =
-        (m0 >= EDIT_GAP_CLASS || edit_base_char(m0) != d) ? 1u : 0u;
-    return e0 | (m1 < EDIT_GAP_CLASS ? 2u : 0u) |
-           (m2 < EDIT_GAP_CLASS ? 4u : 0u) | (m3 < EDIT_GAP_CLASS ? 8u : 0u);
-}
-
-// Is position p inside the stitch window of `state`? first = s0 / 4 and
-// last = (last voted slot) / 4; with no voted ins == 0 slot s0 is INT64_MAX
-// and nothing is inside.
-RK_DEV bool edit_in_window(int64_t p, int64_t n_pos, const long long* state) {
-    const int64_t first = state[0] / VOTE_INS_SLOTS;
-    const int64_t last = state[1] / VOTE_INS_SLOTS;
-    return p < n_pos && p >= first && p <= last;
-}
 
 __global__ __launch_bounds__(EDIT_TILE) void edit_bounds_kernel(
     const uint32_t* __restrict__ table, int64_t n_pos,
@@ -237,22 +200,39 @@ static unsigned edit_blocks(int64_t n_pos) {
 
 int64_t edit_num_blocks(int64_t n_pos) { return edit_blocks(n_pos); }
 
+// state[0], state[1] = first voted ins == 0 slot, last voted slot
+void edit_bounds(const uint32_t* table, int64_t n_pos, int64_t* state,
+                 hipStream_t stream) {
+    if (n_pos <= 0) return;
+    const unsigned blocks = edit_blocks(n_pos);
+    hipLaunchKernelGGL(
+        edit_bounds_kernel,
+        dim3(blocks < EDIT_BOUNDS_BLOCKS ? blocks : EDIT_BOUNDS_BLOCKS),
+        dim3(EDIT_TILE), 0, stream, table, n_pos,
+        reinterpret_cast<long long*>(state));
+}
+
+// counts[0..n) -> exclusive prefix in place; state[2] = their sum
+void edit_scan(int64_t* counts, int64_t n, int64_t* state,
+               hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(edit_scan_kernel, dim3(1), dim3(EDIT_SCAN_THREADS), 0,
+                       stream, reinterpret_cast<long long*>(counts), n,
+                       reinterpret_cast<long long*>(state));
+}
+
 // bounds, count and scan: fills state and turns counts (edit_num_blocks
 // words) into the workgroups' record offsets
 void edit_count(const uint32_t* table, const uint8_t* draft, int64_t n_pos,
                 int64_t* state, int64_t* counts, hipStream_t stream) {
     if (n_pos <= 0) return;
     const unsigned blocks = edit_blocks(n_pos);
-    long long* st = reinterpret_cast<long long*>(state);
-    long long* cn = reinterpret_cast<long long*>(counts);
-    hipLaunchKernelGGL(
-        edit_bounds_kernel,
-        dim3(blocks < EDIT_BOUNDS_BLOCKS ? blocks : EDIT_BOUNDS_BLOCKS),
-        dim3(EDIT_TILE), 0, stream, table, n_pos, st);
+    edit_bounds(table, n_pos, state, stream);
     hipLaunchKernelGGL(edit_count_kernel, dim3(blocks), dim3(EDIT_TILE), 0,
-                       stream, table, draft, n_pos, st, cn);
-    hipLaunchKernelGGL(edit_scan_kernel, dim3(1), dim3(EDIT_SCAN_THREADS), 0,
-                       stream, cn, (int64_t)blocks, st);
+                       stream, table, draft, n_pos,
+                       reinterpret_cast<const long long*>(state),
+                       reinterpret_cast<long long*>(counts));
+    edit_scan(counts, (int64_t)blocks, state, stream);
 }
 
 void edit_write(const uint32_t* table, const uint64_t* qsum,

@@ -23,6 +23,12 @@ Edits (`edits()`, kernels: ops/hip/edits.hip, contract: roko_amd/edits.py):
 from both tables and the draft, the slots at which the polished sequence
 differs from the draft, compacted on the device in slot order; only they are
 copied back.
+
+Stitch (`stitch()`, kernels: ops/hip/stitch.hip, contract: roko_amd/
+stitch.py): the polished sequence and its quality string written on the
+device from the same tables and the draft, with edits below `min_qual`
+rejected and uncovered draft bases kept on request; one byte per polished
+base (two with quality) comes back instead of two per column slot.
 """
 
 from __future__ import annotations
@@ -302,3 +308,51 @@ class DeviceVotes:
         for name in EDIT_DTYPE.names:
             out[name] = rec[name]
         return out
+
+    def stitch(self, contig: str, draft: str, min_qual: int = 0,
+               keep_uncovered: bool = False) -> Tuple[str, Optional[str]]:
+        """The polished contig under the quality filter:
+        stitch.stitch_filtered(draft, *consensus_quality(contig), min_qual,
+        keep_uncovered) computed on the device (ops/hip/stitch.hip). Returns
+        (sequence, Phred+33 quality string); on tables built without quality
+        the quality string is None and `min_qual` must be 0. The draft goes
+        up once (a byte per base); what comes back is three words and then
+        one byte per polished base, and a second one with quality."""
+        from ..quality import unpolished_quality
+        from ..stitch import check_filter
+
+        min_qual, keep_uncovered = check_filter(min_qual, keep_uncovered)
+        self._check()
+        if min_qual > 0:
+            self._need_quality()
+        n_pos = self.lens[contig]
+        if len(draft) != n_pos:
+            raise ValueError(f"{contig}: draft of {len(draft)} bases for "
+                             f"tables of {n_pos}")
+        as_draft = (draft, unpolished_quality(draft) if self.quality
+                    else None)
+        if n_pos == 0 or not self.has_votes(contig):
+            return as_draft
+        n = self.n_slots(contig)
+        table, qsum = self.table(contig), self.qsum(contig)
+        d = torch.from_numpy(
+            np.frombuffer(bytearray(draft, "ascii"), dtype=np.uint8)
+        ).to(self.device)
+        # {first voted ins == 0 slot, last voted slot, polished length}
+        state = torch.tensor([_I64_MAX, -1, 0], dtype=torch.int64) \
+            .to(self.device)
+        offsets = torch.empty(self.ext.edit_num_blocks(n_pos),
+                              dtype=torch.int64, device=self.device)
+        self.ext.stitch_count(table, qsum, d, n, state, offsets, min_qual,
+                              keep_uncovered)
+        s0, _, total = (int(v) for v in state.cpu())
+        if s0 == _I64_MAX:  # no voted ins == 0 slot: nothing is stitched
+            return as_draft
+        seq = torch.empty(total, dtype=torch.uint8, device=self.device)
+        qual = torch.empty(total, dtype=torch.uint8, device=self.device) \
+            if self.quality else None
+        self.ext.stitch_write(table, qsum, d, n, state, offsets, min_qual,
+                              keep_uncovered, seq, qual, total)
+        return (seq.cpu().numpy().tobytes().decode("ascii"),
+                None if qual is None
+                else qual.cpu().numpy().tobytes().decode("ascii"))

@@ -3,6 +3,7 @@
   python -m roko_amd.polish <draft.fasta> <reads.bam> <model.pth> <out.fasta>
       [--t workers] [--b batch] [--seed N] [--extract host|device]
       [--sampler mt19937|counter] [--fastq out.fastq] [--vcf out.vcf]
+      [--min-qual Q] [--keep-uncovered] [--stitch host|device]
 
 Does what `features` followed by `inference` does, and writes the same FASTA
 byte for byte, without the RKW file between them: region windows stream from
@@ -32,6 +33,20 @@ stitch drops because no window covered it is a deletion flagged NOCOV. On
 the GPU routes the edits are compacted on the device from the vote tables
 (ops/hip/edits.hip) and only they come back; the CPU route runs the numpy
 reference. The FASTA and FASTQ do not depend on it.
+
+With --min-qual Q (0..60) only edits of quality Q or more are applied: a
+rejected substitution or deletion leaves the draft base, at Q0, and a rejected
+insertion leaves nothing. With --keep-uncovered a draft base inside the
+polished span that no window covered is kept (Q0) instead of dropped. Either
+option turns the quality tables on; the rules are roko_amd/stitch.py. The VCF
+then lists only the applied edits, under a ##roko_filter header line, so
+applying its records to the draft still gives the FASTA.
+
+With --stitch device (GPU only) the polished sequence and its quality string
+are written on the device from the vote tables (ops/hip/stitch.hip) under the
+same filter, and only polished bytes come back; --stitch host, the default,
+fetches the per-slot consensus and stitches in numpy. Both write the same
+files.
 
 Single process only; for multi-GPU runs use `features` + `inference` under
 torchrun.
@@ -66,11 +81,16 @@ class _DeviceSink:
     stitched from its consensus bytes as soon as its last region is in."""
 
     def __init__(self, model, batch: int, depth: int, lens: Dict[str, int],
-                 quality: bool = False, want_edits: bool = False):
+                 quality: bool = False, want_edits: bool = False,
+                 min_qual: int = 0, keep_uncovered: bool = False,
+                 stitch: str = "host"):
         from .ops.forward import InferencePipeline
         from .ops.votes import DeviceVotes
 
         self.batch = batch
+        # a filter not at its defaults needs quality
+        self.filter = (min_qual, keep_uncovered)
+        self.stitch = stitch
         self.quality = quality
         self.quals: Dict[str, str] = {}  # contig -> quality string
         self.want_edits = want_edits  # needs quality
@@ -111,13 +131,27 @@ class _DeviceSink:
         if not self.dv.has_votes(contig):
             return draft
         if self.want_edits:
-            self.edits[contig] = self.dv.edits(contig, draft)  # drains first
+            from .stitch import applied_edits
+
+            self.edits[contig] = applied_edits(
+                self.dv.edits(contig, draft), *self.filter)  # drains first
+        if self.stitch == "device":
+            seq, qual = self.dv.stitch(contig, draft, *self.filter)
+            self.dv.free(contig)
+            if self.quality:
+                self.quals[contig] = qual
+            return seq
         if self.quality:
             from .quality import stitch_dense_qual
+            from .stitch import is_default, stitch_filtered
 
             maj, qual = self.dv.consensus_quality(contig)  # drains first
             self.dv.free(contig)
-            seq, self.quals[contig] = stitch_dense_qual(draft, maj, qual)
+            if is_default(*self.filter):
+                seq, self.quals[contig] = stitch_dense_qual(draft, maj, qual)
+            else:
+                seq, self.quals[contig] = stitch_filtered(draft, maj, qual,
+                                                          *self.filter)
             return seq
         maj = self.dv.consensus(contig)  # drains the pipeline first
         self.dv.free(contig)
@@ -133,8 +167,10 @@ class _DeviceBuildSink(_DeviceSink):
     windows. A region's last slice may be short."""
 
     def __init__(self, model, batch, depth, lens, cfg, device,
-                 quality=False, want_edits=False):
-        super().__init__(model, batch, depth, lens, quality, want_edits)
+                 quality=False, want_edits=False, min_qual=0,
+                 keep_uncovered=False, stitch="host"):
+        super().__init__(model, batch, depth, lens, quality, want_edits,
+                         min_qual, keep_uncovered, stitch)
         self.cfg, self.device = cfg, device
 
     def add_reads(self, contig: str, pack: dict) -> int:
@@ -156,10 +192,13 @@ class _HostSink:
     batches. Contigs are stitched at the end."""
 
     def __init__(self, model, batch: int, device, drafts: Dict[str, str],
-                 quality: bool = False, want_edits: bool = False):
+                 quality: bool = False, want_edits: bool = False,
+                 min_qual: int = 0, keep_uncovered: bool = False):
         from .inference import StreamingVotes
 
         self.model, self.batch, self.device = model, batch, device
+        # a filter not at its defaults needs quality
+        self.filter = (min_qual, keep_uncovered)
         self.drafts = drafts
         self.quality = quality
         self.quals: Dict[str, str] = {}  # contig -> quality string
@@ -224,21 +263,29 @@ class _HostSink:
             return {name: stitch_contig(self.drafts[name], *tables[name])
                     for name in tables}
         from .quality import stitch_tables
+        from .stitch import (applied_edits, is_default,
+                             stitch_tables_filtered)
 
         tables, sums = self.sv.finalize()
         out = {}
         for name in tables:
-            out[name] = stitch_contig(self.drafts[name], *tables[name])
-            seq, self.quals[name] = stitch_tables(self.drafts[name],
-                                                  tables[name], sums[name])
-            if seq != out[name]:
-                raise RuntimeError(f"{name}: the quality stitch disagrees "
-                                   "with the sequence stitch")
+            if is_default(*self.filter):
+                out[name] = stitch_contig(self.drafts[name], *tables[name])
+                seq, self.quals[name] = stitch_tables(
+                    self.drafts[name], tables[name], sums[name])
+                if seq != out[name]:
+                    raise RuntimeError(f"{name}: the quality stitch "
+                                       "disagrees with the sequence stitch")
+            else:
+                out[name], self.quals[name] = stitch_tables_filtered(
+                    self.drafts[name], tables[name], sums[name],
+                    *self.filter)
             if self.want_edits:
                 from .edits import table_edits
 
-                self.edits[name] = table_edits(self.drafts[name],
-                                               tables[name], sums[name])
+                self.edits[name] = applied_edits(
+                    table_edits(self.drafts[name], tables[name], sums[name]),
+                    *self.filter)
         return out
 
 
@@ -257,6 +304,9 @@ def polish(
     extract: str = "host",
     out_fastq: Optional[str] = None,
     out_vcf: Optional[str] = None,
+    min_qual: int = 0,
+    keep_uncovered: bool = False,
+    stitch: str = "host",
 ) -> Dict[str, str]:
     """Polish `draft_fasta` with the reads in `reads_bam`; returns {contig:
     polished sequence} and writes FASTA if `out_fasta` is given, FASTQ
@@ -265,10 +315,25 @@ def polish(
     FeatureConfig and seeding are those of `features.run`; `depth` is the
     number of in-flight batches on the GPU. `extract="device"` builds the
     windows on the GPU from packed reads (counter sampler, whatever
-    `cfg.sampler` says); it needs a GPU."""
+    `cfg.sampler` says); it needs a GPU. `min_qual` (0..60) applies only the
+    edits of at least that quality and `keep_uncovered` keeps draft bases no
+    window covered (roko_amd/stitch.py); either turns the quality tables on,
+    and the VCF then lists only the applied edits. `stitch="device"` writes
+    the polished sequence and qualities on the GPU (ops/hip/stitch.hip)
+    instead of stitching the fetched consensus in numpy; it needs a GPU."""
+    from .stitch import check_filter
+
     cfg = cfg or FeatureConfig()
+    min_qual, keep_uncovered = check_filter(min_qual, keep_uncovered)
     if extract not in ("host", "device"):
         raise ValueError(f"extract must be 'host' or 'device', got {extract!r}")
+    if stitch not in ("host", "device"):
+        raise ValueError(f"stitch must be 'host' or 'device', got {stitch!r}")
+    if stitch == "device" and _device_type(device) != "cuda":
+        raise ValueError(
+            "stitch='device' writes the polished sequence on the GPU and "
+            f"needs a GPU device (got {_device_type(device)!r}); use "
+            "stitch='host'")
     if extract == "device":
         from .ops.windows import check_geometry
 
@@ -294,7 +359,7 @@ def polish(
     try:
         return _polish(refs, jobs, pool, model_path, out_fasta, workers,
                        batch_size, device, model, log, depth, extract, cfg,
-                       out_fastq, out_vcf)
+                       out_fastq, out_vcf, min_qual, keep_uncovered, stitch)
     finally:
         if pool is not None:
             pool.terminate()
@@ -312,7 +377,8 @@ def _device_type(device) -> str:
 
 def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
             device, model, log, depth, extract, cfg,
-            out_fastq=None, out_vcf=None) -> Dict[str, str]:
+            out_fastq=None, out_vcf=None, min_qual=0, keep_uncovered=False,
+            stitch="host") -> Dict[str, str]:
     import torch
 
     from .model import RokoModel
@@ -326,19 +392,25 @@ def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
     model = model.to(device).eval()
 
     drafts = dict(refs)
-    # the edits carry qualities, so a VCF turns the quality tables on
-    quality = bool(out_fastq or out_vcf)
+    # the edits carry qualities, so a VCF turns the quality tables on; so
+    # does a filter not at its defaults, which is decided per slot from them
+    from .stitch import is_default, vcf_header
+
+    quality = bool(out_fastq or out_vcf
+                   or not is_default(min_qual, keep_uncovered))
     want_edits = bool(out_vcf)
     if extract == "device":
         sink = _DeviceBuildSink(model, batch_size, depth,
                                 {n: len(s) for n, s in refs}, cfg, device,
-                                quality, want_edits)
+                                quality, want_edits, min_qual, keep_uncovered,
+                                stitch)
     elif device.type == "cuda":
         sink = _DeviceSink(model, batch_size, depth,
-                           {n: len(s) for n, s in refs}, quality, want_edits)
+                           {n: len(s) for n, s in refs}, quality, want_edits,
+                           min_qual, keep_uncovered, stitch)
     else:
         sink = _HostSink(model, batch_size, device, drafts, quality,
-                         want_edits)
+                         want_edits, min_qual, keep_uncovered)
     worker = generate_reads if extract == "device" else generate_infer
     log(f"polish: {len(jobs)} region jobs, {workers} workers, "
         f"batch {batch_size}, windows on {extract}, votes on {device.type}")
@@ -406,7 +478,8 @@ def _polish(refs, jobs, pool, model_path, out_fasta, workers, batch_size,
 
         # a contig without windows has no edits, only its ##contig line
         n = write_vcf(out_vcf, [(name, len(seq)) for name, seq in refs],
-                      contig_vcf_records(refs, sink.edits))
+                      contig_vcf_records(refs, sink.edits),
+                      vcf_header(min_qual, keep_uncovered))
         log(f"wrote {n} records of "
             f"{sum(len(e) for e in sink.edits.values())} edits to {out_vcf}")
     return out
@@ -434,10 +507,22 @@ def main(argv=None):
     p.add_argument("--vcf", default=None, metavar="PATH",
                    help="also write VCF: the edits between the draft and "
                         "the polished sequence, with their qualities")
+    p.add_argument("--min-qual", type=int, default=0, metavar="Q",
+                   help="apply only edits of quality Q or more (0..60); a "
+                        "rejected edit leaves the draft as it was, at Q0")
+    p.add_argument("--keep-uncovered", action="store_true",
+                   help="keep draft bases inside the polished span that no "
+                        "window covered (Q0) instead of dropping them")
+    p.add_argument("--stitch", choices=("host", "device"), default="host",
+                   help="where the polished sequence is put together: numpy "
+                        "over the fetched consensus (host) or the GPU, so "
+                        "that only polished bytes come back (device)")
     a = p.parse_args(argv)
     polish(a.draft, a.bam, a.model, a.out, workers=a.t, batch_size=a.b,
            cfg=FeatureConfig(seed=a.seed, sampler=a.sampler),
-           extract=a.extract, out_fastq=a.fastq, out_vcf=a.vcf)
+           extract=a.extract, out_fastq=a.fastq, out_vcf=a.vcf,
+           min_qual=a.min_qual, keep_uncovered=a.keep_uncovered,
+           stitch=a.stitch)
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""End-to-end polishing rate: draft + BAM -> FASTA, six ways.
+"""End-to-end polishing rate: draft + BAM -> FASTA, seven ways.
 
   python scripts/polish_bench.py [--ref-len N] [--cov C] [--t WORKERS]
       [--b BATCH] [--limit SECONDS] [--dir DIR] [--routes a,b,...]
@@ -15,6 +15,8 @@ _make_case, size given by --ref-len), then times
                         windows are built on the GPU (counter sampler)
   polish_device_vcf     polish_device with out_vcf: quality tables on, the
                         edits compacted on the GPU, the VCF written
+  polish_device_stitch  polish_device with stitch="device" and a FASTQ: the
+                        polished sequence and qualities written on the GPU
 
 --routes picks a subset; --repeat N runs the chosen routes N times in turn
 (a, b, a, b, ...), so that drift of the machine hits all of them alike.
@@ -48,7 +50,7 @@ sys.path.insert(0, ROOT)
 
 STEPS = ("two_step", "infer_device", "polish")
 COUNTER_STEPS = ("polish_host_counter", "polish_device",
-                 "polish_device_vcf")
+                 "polish_device_vcf", "polish_device_stitch")
 ALL_STEPS = STEPS + COUNTER_STEPS
 
 
@@ -94,7 +96,7 @@ def run_step(step, d, workers, batch, region, fastq=False):
     rec = {"step": step, "workers": workers, "batch": batch,
            "draft_bases": draft_bases}
     out_fastq = None
-    if fastq and step != "two_step":
+    if (fastq and step != "two_step") or step == "polish_device_stitch":
         out_fastq = os.path.join(d, f"{step}.fastq")
         rec.update(fastq=True,
                    qsum_bytes=8 * (C.MAX_INS + 1) * draft_bases)
@@ -112,7 +114,8 @@ def run_step(step, d, workers, batch, region, fastq=False):
                cfg=cfg, log=quiet,
                extract="device" if step.startswith("polish_device")
                else "host",
-               out_fastq=out_fastq, out_vcf=out_vcf)
+               out_fastq=out_fastq, out_vcf=out_vcf,
+               stitch="device" if step == "polish_device_stitch" else "host")
         n = LAST_RUN["windows"]
     else:
         rkw = os.path.join(d, f"{step}.rkw")
